@@ -15,7 +15,9 @@ the rest, the per-cell stats, the reference-allele tallies and, for N > 1, their
 RCCL all-reduce; the 16-bit count rows go to pinned host memory as their windows
 complete. `value` = reads of all ranks x K / the slowest rank's time for K steps.
 
-Beside it (never inside the timed steps), the line carries:
+A plain run does only that: it sets up, warms up, times the K steps, writes its
+outputs when --dump-outputs is given, and prints the line. With --full, beside it
+(never inside the timed steps), the line carries:
   * device: the same hot path with the inputs already resident in HBM (K x
     mgp_run, results left in HBM) on the 32-byte records whose per-base filter the
     producer resolved (value_device, its stage times and per-kernel rooflines),
@@ -75,6 +77,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the bit-exact sample checks against the oracle, "
+                         "the HBM-resident device legs and their per-stage runs, the extra streamed legs, the host "
+                         "pack timing, the CPU baseline and the end-to-end leg (each can be skipped with its --no-* "
+                         "option); off by default: a plain run times the headline step alone")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step delivered as DIR/<name>.npy (float64): "
+                         "the per-cell statistics and reference tallies of every cell and the count rows of a "
+                         "fixed, seeded sample of cells")
     ap.add_argument("--reads", type=int, default=200_000_000, help="reads of the whole set (all GPUs)")
     ap.add_argument("--cells", type=int, default=10_000, help="cells of the whole set (all GPUs)")
     ap.add_argument("--read-len", type=int, default=50)
@@ -258,27 +269,29 @@ def main():
     # on the 32-byte records whose per-base filter the producer resolved (value_device)
     # and on the 64-byte records the kernel filters (device_paired)
     dev = None
-    if not args.no_device:
-        dev = device_leg(ctx, args.record_layout)
+    if (args.full or args.device_only) and not args.no_device:
+        dev = device_leg(ctx, args.record_layout, headline=head is None)
+    if head is None and dev is None:
+        raise SystemExit("--device-only with --no-device leaves nothing to time")
     paired = None
-    if not args.device_only and not args.no_device_paired and args.record_layout != "paired":
+    if args.full and not args.device_only and not args.no_device_paired and args.record_layout != "paired":
         paired = device_leg(ctx, "paired")
     host_pack = None
-    if rank == 0 and not args.no_host_pack:
+    if args.full and rank == 0 and not args.no_host_pack:
         host_pack = host_pack_leg(args, cfg, device)
     # the streamed leg on the 32-byte records and the batch-size sweep (untimed extras)
     pcie_more = None
-    if not args.no_pcie:
+    if args.full and not args.no_pcie:
         sweep = batch_sizes(args.batch_reads)
         pcie_more = stream_leg(ctx, "pack32", sweep[:1], timed=False)
         if len(sweep) > 1 and not args.device_only:
             pcie_more["sweep_" + args.layout] = stream_leg(ctx, args.layout, sweep, timed=False)["legs"]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, cfg, local_rank)
 
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e and not args.device_only:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e and not args.device_only:
         e2e = e2e_leg(args)
 
     if rank == 0:
@@ -419,10 +432,12 @@ def stream_kernels(n: int, nc: int) -> dict | None:
     return None
 
 
-def device_leg(ctx: Ctx, layout: str) -> dict:
+def device_leg(ctx: Ctx, layout: str, headline: bool = False) -> dict:
     """The hot path with its inputs resident in HBM: K runs of mgp_run (untimed
-    generation on the device), ms per step (max over ranks), the stage times, the
-    per-kernel rooflines and, on rank 0, the bit-exact sample check."""
+    generation on the device), ms per step (max over ranks) and the pileup's
+    roofline; with --full also the stage times and per-kernel rooflines of a few
+    more runs and, on rank 0, the bit-exact sample check. headline (--device-only):
+    this leg is the line, and --dump-outputs writes its results."""
     from mgatk2_amd.bam import PLACE_PAIRED, place_records
     from mgatk2_amd.engine import Engine
 
@@ -465,13 +480,17 @@ def device_leg(ctx: Ctx, layout: str) -> dict:
     dt_rank = time.perf_counter() - t0
     dt = ctx.reduce(dt_rank, "max")
     kt = eng.kernel_times(last_runs=min(args.steps, 64))
-    # the per-stage breakdown from a few more (untimed) runs with every stage bracketed
-    eng.set_stage_timing(True)
-    for _ in range(3):
-        eng.run()
-    eng.sync()
-    kt_all = eng.kernel_times(last_runs=3)
     res = eng.fetch(dense=False)
+    if headline and args.dump_outputs:
+        dump_outputs(ctx, res, lambda c: eng.fetch_cells(c, c + 1).__dict__)
+    kt_all = kt
+    if args.full:
+        # the per-stage breakdown from a few more (untimed) runs with every stage bracketed
+        eng.set_stage_timing(True)
+        for _ in range(3):
+            eng.run()
+        eng.sync()
+        kt_all = eng.kernel_times(last_runs=3)
     nc = cfg.n_cells
     # roofline of the dominant kernel: its own algorithmic bytes per launch over its
     # HIP-event time on the compute stream, averaged over the timed steps; the whole
@@ -483,7 +502,7 @@ def device_leg(ctx: Ctx, layout: str) -> dict:
     step_achieved = engine_bytes / (dt_rank / args.steps) / 1e9
     pmc = pmc_traffic("device", n_res, nc, layout)
     check = None
-    if ctx.rank == 0 and not args.no_check:
+    if args.full and ctx.rank == 0 and not args.no_check:
         check = sample_check(eng, cfg, res, args, ctx.seed, ctx.cdf, ctx.ref, ctx.cell0, ctx.device)
     eng.close()
     return {
@@ -514,6 +533,30 @@ def device_leg(ctx: Ctx, layout: str) -> dict:
         "error_bits": res.stats["error_bits"],
         "sample_check": check,
     }
+
+
+DUMP_CELLS = 32  # count rows of 32 cells as float64: 32 x 16569 x 11 x 8 B = 47 MB, under the 64 MB a dump may hold
+
+
+def dump_outputs(ctx: Ctx, res, rows_of_cell) -> None:
+    """--dump-outputs: what the last timed step delivered, as DIR/<name>.npy (float64;
+    <name>_rank<r> when there are several ranks): the per-cell statistics and the
+    reference tallies whole, and the count rows (counts, tn5, depth) of DUMP_CELLS
+    cells of the rank, drawn with the run's seed (`cells` holds their indices).
+    rows_of_cell(c) gives cell c's u32 rows as the step left them on the host."""
+    out = Path(ctx.args.dump_outputs)
+    out.mkdir(parents=True, exist_ok=True)
+    nc = ctx.cfg.n_cells
+    cells = np.sort(np.random.default_rng(ctx.args.seed).choice(nc, size=min(nc, DUMP_CELLS), replace=False))
+    arrays = {k: getattr(res, k) for k in ("n_reads", "any_paired", "passed", "covered", "depth_sum", "depth_max",
+                                           "median_lo", "median_hi", "ref_tally")}
+    arrays["cells"] = cells
+    rows = [rows_of_cell(int(c)) for c in cells]
+    for k in ("counts", "tn5", "depth"):
+        arrays[k] = np.concatenate([r[k] for r in rows])
+    suffix = "" if ctx.world == 1 else f"_rank{ctx.rank}"
+    for k, a in arrays.items():
+        np.save(out / f"{k}{suffix}.npy", np.asarray(a, dtype=np.float64))
 
 
 def host_pack_leg(args, cfg, device, n: int = 4_000_000) -> dict:
@@ -862,7 +905,9 @@ def stream_leg(ctx: Ctx, layout: str, batch_list: list, timed: bool) -> dict:
     pmc = pmc_traffic("stream", n, nc, layout)
     step_s = dt_rank / args.steps
     check = None
-    if ctx.rank == 0 and not args.no_check:
+    if args.dump_outputs:
+        dump_outputs(ctx, res, lambda c: ss.cells(c, c + 1))
+    if args.full and ctx.rank == 0 and not args.no_check:
         check = sample_check(eng, cfg, res, args, ctx.seed, ctx.cdf, ctx.ref, ctx.cell0, ctx.device, delivered=ss)
     wide_cells = len(ss.exact)
     d2h = ss.d2h_bytes()

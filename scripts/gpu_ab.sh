@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 V=${1:?variant .so}
-A="python bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+A="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 for r in 1 2; do
   timeout -k 10 300 $A > gpurun_out/ab_base_$r.log 2>&1 || exit $?
   MGP_LIB=$V timeout -k 10 300 $A > gpurun_out/ab_var_$r.log 2>&1 || exit $?

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-A="python bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+A="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 timeout -k 10 300 $A > gpurun_out/abl_0warm.log 2>&1 || exit $?
 timeout -k 10 300 $A > gpurun_out/abl_1base.log 2>&1 || exit $?
 for v in "$@"; do

@@ -3,7 +3,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-A="python bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+A="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 for r in 1 2; do
   for lay in ${LAYOUTS:-paired packed}; do
     timeout -k 10 300 $A --record-layout $lay > gpurun_out/lay_${lay}_$r.log 2>&1 || exit $?

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 KRE=${KRE:-"k_pileup|k_scatter|k_bin_hist|k_median"}
-ARGS=${ARGS:-"--steps 2 --warmup 0 --no-cpu-baseline"}
+ARGS=${ARGS:-"--full --steps 2 --warmup 0 --no-cpu-baseline"}
 timeout -k 10 120 rocprofv3 -L > gpurun_out/counters_list.txt 2>&1 || true
 i=0
 while read -r grp; do

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for lay in packed full; do
     timeout -s KILL 300 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum \
         TCC_EA0_RDREQ_128B_sum --kernel-include-regex "k_pileup" --output-format csv -d gpurun_out/rdreq_$lay -o pmc \
-        -- python bench.py --steps 2 --warmup 0 --no-cpu-baseline --record-layout $lay \
+        -- python bench.py --full --steps 2 --warmup 0 --no-cpu-baseline --record-layout $lay \
         > gpurun_out/rdreq_$lay.log 2>&1 || exit $?
 done
 python - <<'PY'

@@ -19,9 +19,9 @@ step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
 step pytest_gpu 900 python -m pytest tests -m gpu -q -x -p no:cacheprovider
 rc=$?; [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 [ "$MODE" = "tests" ] && exit 0
-step bench 600 python bench.py --steps 10 --warmup 2 || exit $?
+step bench 600 python bench.py --full --steps 10 --warmup 2 || exit $?
 [ "$MODE" = "bench" ] && exit 0
 step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- \
-    python bench.py --steps 5 --warmup 1 --no-cpu-baseline || exit $?
+    python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline || exit $?
 find gpurun_out/prof -name "*kernel_stats.csv" -exec cp {} gpurun_out/kernel_stats.csv \;
 cat gpurun_out/kernel_stats.csv | cut -c1-200

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 KRE=${KRE:-"k_pileup|k_scatter|k_bin_count"}
-ARGS=${ARGS:-"--steps 2 --warmup 0 --no-cpu-baseline"}
+ARGS=${ARGS:-"--full --steps 2 --warmup 0 --no-cpu-baseline"}
 i=0
 while read -r grp; do
     [ -z "$grp" ] && continue

@@ -13,6 +13,7 @@ while read -r grp; do
         if [ "$lib" = base ]; then unset MGP_LIB; else export MGP_LIB=mgatk2_amd/_lib/$lib; fi
         timeout -k 10 300 rocprofv3 --pmc $grp --kernel-include-regex "k_pileup" --output-format csv \
             -d gpurun_out/sq_${lib}_$i -o pmc -- python bench.py --steps 2 --warmup 0 --no-cpu-baseline \
+            --full \
             > gpurun_out/sq_${lib}_$i.log 2>&1 || exit $?
     done
 done <<'GROUPS'

@@ -12,6 +12,7 @@ for grp in "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" "TCC_EA0_RDREQ_sum TCC_EA0_
     i=$((i + 1))
     timeout -s KILL 120 rocprofv3 --pmc $grp --kernel-include-regex "$K" --output-format csv \
         -d gpurun_out/tcc_${TAG}_$i -o pmc -- python bench.py --steps 2 --warmup 0 --no-cpu-baseline \
+        --full \
         > gpurun_out/tcc_${TAG}_$i.log 2>&1 || exit $?
 done
 python - "$TAG" <<'PY'

@@ -146,3 +146,40 @@ def test_bench_kernel_bytes_follow_the_record_layout():
         assert b["group_b"] == 12 * 1000
     kr = bench.kernel_rooflines({"pileup": 1.0}, 2000, 10, st, cfg, "quad32")
     assert set(kr) == {"pileup"} and kr["pileup"]["alg_bytes"] == 36 * 1000 + bench.ROW16_BYTES_PER_CELL * 10
+
+
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: float64 arrays, the whole per-cell statistics and the rows of a
+    sample of cells drawn with the run's seed (the same cells in every run), within the
+    64 MB a dump may hold at the bench's full size; --full is off in a plain run."""
+    import numpy as np
+
+    import bench
+    from mgatk2_amd.engine import EngineConfig, EngineResult
+
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    cfg = EngineConfig(n_cells=100)
+    L = cfg.mito_len
+    res = EngineResult.alloc(100, L, dense=False)
+    res.n_reads[:] = np.arange(100)
+    rows = lambda c: {"counts": np.full((1, L, 8), c, np.uint32), "tn5": np.zeros((1, L, 2), np.uint32),
+                      "depth": np.full((1, L), 2 * c, np.uint32)}
+    got = []
+    for d in ("a", "b"):
+        args.dump_outputs = str(tmp_path / d)
+        ctx = bench.Ctx(args, cfg, args.seed, None, None, {}, 0, None, None, None, 0, 1, 0)
+        bench.dump_outputs(ctx, res, rows)
+        got.append({f.stem: np.load(f) for f in sorted((tmp_path / d).glob("*.npy"))})
+    a, b = got
+    assert set(a) == {"n_reads", "any_paired", "passed", "covered", "depth_sum", "depth_max", "median_lo",
+                      "median_hi", "ref_tally", "cells", "counts", "tn5", "depth"}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    cells = a["cells"].astype(int)
+    assert len(set(cells)) == bench.DUMP_CELLS and a["counts"].shape == (bench.DUMP_CELLS, L, 8)
+    assert np.array_equal(a["counts"][:, 0, 0], cells) and np.array_equal(a["depth"][:, 5], 2 * cells)
+    assert np.array_equal(a["n_reads"], np.arange(100))
+    # at C4 (10k cells): the sampled rows plus every per-cell and per-position array
+    assert bench.DUMP_CELLS * L * 11 * 8 + 10_000 * 8 * 8 + L * 4 * 8 + bench.DUMP_CELLS * 8 <= 64 * 10**6
