@@ -129,6 +129,13 @@ struct H5State {
 enum Stage { ST_HIST, ST_SCAN, ST_GROUP_A, ST_GROUP_B, ST_PILEUP, ST_GATE, ST_MEDIAN, ST_TALLY, ST_COMM, ST_N };
 static const char* kStageNames = "hist,scan,group_a,group_b,pileup,gate,median,tally,comm";
 
+// paced rows (RowsPace): the default of MGP_ROWS_SPREAD, and the longest budget of one
+// launch, whatever the knob or the ring hold
+#ifndef MGP_ROWS_SPREAD_DEFAULT
+#define MGP_ROWS_SPREAD_DEFAULT 0.5f
+#endif
+constexpr int kRowsPaceMaxMs = 20;
+
 struct mgp_ctx {
     mgp_config cfg{};
     int dev = 0;
@@ -147,6 +154,18 @@ struct mgp_ctx {
     hipEvent_t ev_copy = nullptr, ev_fork = nullptr, ev_join = nullptr;
     int seg_min_win = 1;     // a streaming push queues a segment once this many windows are complete (MGP_SEG_MIN_WIN)
     int rows_wg = 256;       // workgroups of a segment's k_rows_to_host (MGP_ROWS_WG)
+    // paced rows (rows_copy): a streaming segment's rows kernel spreads its stores over
+    // rows_spread of the interval since the previous segment's rows kernel started
+    // (MGP_ROWS_SPREAD; 0: every rows kernel runs free), with rows_wg_paced workgroups
+    // (MGP_ROWS_WG_PACED). rows_ring: the kernels' start stamps (wall_clock64) by
+    // rows_seq % kRowsRing; rows_chain: the previous rows kernel of this run left a stamp
+    static constexpr int kRowsRing = 16;
+    float rows_spread = MGP_ROWS_SPREAD_DEFAULT;
+    int rows_wg_paced = 64;
+    unsigned rows_max_ticks = 0;  // the longest budget of one paced launch (kRowsPaceMaxMs)
+    DevBuf rows_ring;
+    int64_t rows_seq = 0;
+    bool rows_chain = false;
     int32_t cell_lo = 0;     // mgp_set_cell_range: the context's cells in the pushed batches' barcode indices
     bool cell_range = false;
     int pile_wg_stream = 0;  // a streaming run's pileup workgroups per window (set_pile_chunks; 0: the default)
@@ -2831,16 +2850,63 @@ __global__ void __launch_bounds__(kBlock) k_expand(Geom g, int64_t p0, int64_t n
     if (depth) depth[P] = o16.depth[P];
 }
 
+// Pacing of a streaming segment's rows kernel. Stores to host memory are posted: a few
+// hundred waves fill the link's upstream direction whatever the grid, and the H2D copies
+// beside them lose a quarter of their rate for as long as the kernel runs (their read
+// requests travel upstream too). Held to 40 GB/s or less the same stores leave the copies
+// at their full rate (scripts/probe_pcie.hip). So a segment's rows leave
+// over a fraction of the time the next segment takes to arrive: every rows kernel of a
+// streaming run stamps its start (wall_clock64) into a ring slot, and the next one spreads
+// its stores over f x (its own start - that stamp), each workgroup on its own schedule from
+// its own start. A kernel queued behind a late predecessor sees only the predecessor's
+// duration as its interval, so the budget shrinks by f per segment and rows that outweigh
+// the reads cannot build a backlog. prev == nullptr runs free.
+struct RowsPace {
+    const unsigned long long* prev;  // the previous rows kernel's start stamp (nullptr: run free)
+    unsigned long long* mine;        // where this kernel leaves its own (nullptr: nowhere)
+    float f;                         // the fraction of the interval to spread over
+    unsigned max_ticks;              // kRowsPaceMaxMs in wall-clock ticks
+};
+
+// A workgroup's schedule: its iteration j of n is not stored before t0 + (j + phase) * step
+struct RowsSched {
+    unsigned long long t0;
+    float step, phase;
+    __device__ __forceinline__ void init(const RowsPace& pc, int nc) {
+        step = 0.f;
+        if (!pc.prev && !pc.mine) return;
+        t0 = wall_clock64();
+        if (pc.mine && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *pc.mine = t0;
+        if (!pc.prev) return;
+        // (a stamp that is not behind t0 wraps to a huge interval: the ceiling holds)
+        const float budget = fminf(pc.f * (float)(t0 - *pc.prev), (float)pc.max_ticks);
+        const int n = (nc - (int)blockIdx.y + (int)gridDim.y - 1) / (int)gridDim.y;
+        step = budget / (float)max(n, 1);
+        phase = (float)blockIdx.y / (float)gridDim.y;  // the workgroups take turns within a step
+    }
+    // every wait ends within the budget: (j + phase) * step < n * step = budget <= max_ticks
+    __device__ __forceinline__ void wait(int j) const {
+        if (step <= 0.f) return;
+        const unsigned long long due = (unsigned long long)(((float)j + phase) * step);
+        while (wall_clock64() - t0 < due) __builtin_amdgcn_s_sleep(16);
+    }
+};
+
 // mgp_set_rows16_target: positions [p0, p1) of every cell's 16-bit rows into the pinned
 // host target (device-mapped: vector stores over PCIe, consecutive lanes consecutive
 // addresses, so they leave as full-width writes)
 __global__ void __launch_bounds__(kBlock) k_rows_to_host(int L, int nc, int p0, int p1, const uint4* __restrict__ c16,
                                                          const uint32_t* __restrict__ t16,
                                                          const uint16_t* __restrict__ d16, uint4* __restrict__ hc,
-                                                         uint32_t* __restrict__ ht, uint16_t* __restrict__ hd) {
+                                                         uint32_t* __restrict__ ht, uint16_t* __restrict__ hd,
+                                                         RowsPace pace) {
+    RowsSched sc;
+    sc.init(pace, nc);
     const int p = p0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (p >= p1) return;
-    for (int c = blockIdx.y; c < nc; c += gridDim.y) {
+    int j = 0;
+    for (int c = blockIdx.y; c < nc; c += gridDim.y, ++j) {
+        sc.wait(j);
         const size_t P = (size_t)c * L + p;
         hc[P] = c16[P];
         ht[P] = t16[P];
@@ -2862,11 +2928,15 @@ __global__ void __launch_bounds__(kBlock) k_rows_to_host8(int L, int nc, int p0,
                                                           const uint8_t* __restrict__ fit8, uint4* __restrict__ hc,
                                                           uint32_t* __restrict__ ht, uint16_t* __restrict__ hd,
                                                           uint2* __restrict__ hc8, uint16_t* __restrict__ ht8,
-                                                          uint8_t* __restrict__ hd8) {
+                                                          uint8_t* __restrict__ hd8, RowsPace pace) {
+    RowsSched sc;
+    sc.init(pace, nc);
     const int p = p0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (p >= p1) return;
     const int k = p / W;
-    for (int c = blockIdx.y; c < nc; c += gridDim.y) {
+    int j = 0;
+    for (int c = blockIdx.y; c < nc; c += gridDim.y, ++j) {
+        sc.wait(j);
         const size_t P = (size_t)c * L + p;
         const uint4 a = c16[P];
         const uint32_t t = t16[P];
@@ -3333,6 +3403,21 @@ int mgp_open(const mgp_config* cfg, int hip_device, mgp_ctx** out) {
     for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_stage[i], hipEventDisableTiming));
     if (const char* e = std::getenv("MGP_SEG_MIN_WIN")) ctx->seg_min_win = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("MGP_ROWS_WG")) ctx->rows_wg = std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("MGP_ROWS_SPREAD")) {
+        const float f = std::strtof(e, nullptr);
+        ctx->rows_spread = f > 0.f ? std::min(f, 1.f) : 0.f;  // (a NaN reads as 0: unpaced)
+    }
+    if (const char* e = std::getenv("MGP_ROWS_WG_PACED")) ctx->rows_wg_paced = std::max(1, std::atoi(e));
+    {
+        int khz = 0;  // wall_clock64's rate (100 MHz on gfx950)
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, hip_device) != hipSuccess || khz <= 0) {
+            (void)hipGetLastError();
+            khz = 100000;
+        }
+        ctx->rows_max_ticks = (unsigned)std::min<int64_t>((int64_t)khz * kRowsPaceMaxMs, 0x7FFFFFFF);
+        MGP_TRY(ctx->rows_ring.ensure(mgp_ctx::kRowsRing * 8));
+        HIP_TRY(hipMemset(ctx->rows_ring.p, 0, mgp_ctx::kRowsRing * 8));
+    }
     ctx->pile_wg_stream = MGP_PILE_WG_STREAM;
     if (const char* e = std::getenv("MGP_PILE_WG_STREAM")) ctx->pile_wg_stream = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("MGP_PILE_MIN_CPB_STREAM")) ctx->pile_min_cpb_stream = std::max(1, std::atoi(e));
@@ -3743,21 +3828,22 @@ struct Seg {
 
 // k_rows_to_host (or k_rows_to_host8 with an 8-bit target) over positions [p0, p1) on the
 // D2H stream
-static int rows_launch(mgp_ctx* ctx, dim3 gr, int p0, int p1) {
+static int rows_launch(mgp_ctx* ctx, dim3 gr, int p0, int p1, const RowsPace& pace = RowsPace{}) {
     const Geom& g = ctx->g;
     const mgp_rows16& t = ctx->rows_tgt;
+    if (!pace.mine) ctx->rows_chain = false;  // (no stamp: the next paced kernel has no interval)
     if (ctx->rows8_on) {
         const mgp_rows8& t8 = ctx->rows8_tgt;
         k_rows_to_host8<<<gr, kBlock, 0, ctx->s_d2h>>>(
             g.L, g.nc, p0, p1, g.W, g.nwin, ctx->counts16.as<uint4>(), ctx->tn5_16.as<uint32_t>(),
             ctx->depth16.as<uint16_t>(), ctx->fit8.as<uint8_t>(), reinterpret_cast<uint4*>(t.counts),
             reinterpret_cast<uint32_t*>(t.tn5), t.depth, reinterpret_cast<uint2*>(t8.counts),
-            reinterpret_cast<uint16_t*>(t8.tn5), t8.depth);
+            reinterpret_cast<uint16_t*>(t8.tn5), t8.depth, pace);
     } else {
         k_rows_to_host<<<gr, kBlock, 0, ctx->s_d2h>>>(g.L, g.nc, p0, p1, ctx->counts16.as<uint4>(),
                                                     ctx->tn5_16.as<uint32_t>(), ctx->depth16.as<uint16_t>(),
                                                     reinterpret_cast<uint4*>(t.counts),
-                                                    reinterpret_cast<uint32_t*>(t.tn5), t.depth);
+                                                    reinterpret_cast<uint32_t*>(t.tn5), t.depth, pace);
     }
     HIP_TRY(hipGetLastError());
     return MGP_OK;
@@ -3767,18 +3853,41 @@ static int rows_launch(mgp_ctx* ctx, dim3 gr, int p0, int p1) {
 // stream behind the compute stream's work so far (mgp_set_rows16_target): written by a
 // kernel into the mapped pinned target (a strided 2D copy of 10k rows per segment runs as
 // row-by-row DMA transfers: 4x slower overall)
-static int rows_copy(mgp_ctx* ctx, int p0, int p1) {
+//
+// stream: a streaming segment with more segments to come (run_segment): its kernel stamps
+// its start and, from the run's second segment on, paces its stores (RowsPace). The run's
+// last segment and a resident run's rows (run_finish) run free: no copy is left to disturb.
+static int rows_copy(mgp_ctx* ctx, int p0, int p1, bool stream = false, bool first = false) {
     const Geom& g = ctx->g;
     const int nc = g.nc;
     HIP_TRY(hipEventRecord(ctx->ev_rows, ctx->s_comp));
     HIP_TRY(hipStreamWaitEvent(ctx->s_d2h, ctx->ev_rows, 0));
+    RowsPace pace{};
+    int wg = ctx->rows_wg;
+    if (stream && ctx->rows_spread > 0.f) {
+        unsigned long long* ring = ctx->rows_ring.as<unsigned long long>();
+        pace.mine = ring + ctx->rows_seq % mgp_ctx::kRowsRing;
+        if (!first && ctx->rows_chain) {
+            pace.prev = ring + (ctx->rows_seq + mgp_ctx::kRowsRing - 1) % mgp_ctx::kRowsRing;
+            pace.f = ctx->rows_spread;
+            pace.max_ticks = ctx->rows_max_ticks;
+            // a sleeping wave holds its slot for the whole budget: no more workgroups than
+            // the paced rate needs (64 x 256 lanes keep some 180 KB in flight)
+            wg = std::min(wg, ctx->rows_wg_paced);
+        }
+    }
     // a few hundred workgroups looping over the cells: the stores wait on the host
     // link, and a grid of one workgroup per (cell, 256 positions) held every CU
     // slot of the device while they drained, starving the kernels of the next
     // segment and the run's medians (MGP_ROWS_WG)
     const unsigned gx = (unsigned)((p1 - p0 + kBlock - 1) / kBlock);
-    dim3 gr(gx, (unsigned)std::max(1, std::min(std::min(nc, 65535), ctx->rows_wg / (int)gx)));
-    return rows_launch(ctx, gr, p0, p1);
+    dim3 gr(gx, (unsigned)std::max(1, std::min(std::min(nc, 65535), wg / (int)gx)));
+    MGP_TRY(rows_launch(ctx, gr, p0, p1, pace));
+    if (pace.mine) {
+        ++ctx->rows_seq;
+        ctx->rows_chain = true;
+    }
+    return MGP_OK;
 }
 
 static int run_segment(mgp_ctx* ctx, const Seg& sg, int slot, int& dup_parts, int& pair_mode) {
@@ -4070,7 +4179,7 @@ static int run_segment(mgp_ctx* ctx, const Seg& sg, int slot, int& dup_parts, in
                 ctx->rows_p1 = p1;
                 ctx->rows_pending = true;
             } else {
-                MGP_TRY(rows_copy(ctx, p0, p1));
+                MGP_TRY(rows_copy(ctx, p0, p1, sg.stream, sg.first));
             }
         }
     }
