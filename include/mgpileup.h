@@ -59,7 +59,10 @@ extern "C" {
                               6: mgp_txt_gz_* (the txt count files formatted and deflated on the
                                  device);
                               7: mgp_set_rows_target (an 8-bit rows target beside the 16-bit one),
-                                 mgp_h5_tiles_* (the HDF5 chunks deflated on the device) */
+                                 mgp_h5_tiles_* (the HDF5 chunks deflated on the device);
+                                 added since, additive only (the version stays 7):
+                                 mgp_variant_moments_*, mgp_variant_dev2_*, mgp_allele_freq_*
+                                 (variant statistics and heteroplasmy on the device) */
 
 /* ---- return codes (0 = success) ------------------------------------------ */
 #define MGP_OK               0
@@ -583,6 +586,59 @@ typedef struct mgp_h5_tiles {
 } mgp_h5_tiles;
 int  mgp_h5_tiles_run(mgp_ctx *ctx, mgp_h5_tiles *job, int64_t *total_bytes);
 int  mgp_h5_tiles_fetch(mgp_ctx *ctx, uint8_t *dst, int64_t cap);
+/* Variant statistics and heteroplasmy on the device (added under ABI 7). Replaces the R
+ * step mgatk users run on counts.h5, identify_variants and calculate_allele_freq
+ * (R/mgatk2_functions.R:282-372): reductions over the cells of the run's strand-filtered
+ * count rows, which are still in HBM. Per cell c, position p and base b (A, C, G, T):
+ * f, r = the fwd and rev counts (mgp_result.counts), cov = the filtered depth
+ * (mgp_result.depth), af = (f + r) / cov in fp64 (0 where cov == 0). Values are the
+ * engine's exact counts (counts.h5 stores min(v, 65535)).
+ * A call's population is `cells`, in that order: the context's cell index of each, -1 = an
+ * all-zero row (a whitelist column without a written cell); NULL = every cell of the
+ * context, in index order (n_cells is then ignored). Exactness bound: a call takes at most
+ * 65,536 cells, and every fwd / rev count of its cells must be below 2^24 (then every u64
+ * moment is exact: 2^16 terms below 2^48); otherwise MGP_E_INVALID, nothing wraps. Larger
+ * populations go in several calls whose moments are added. */
+typedef struct mgp_variant_job {
+    int64_t        n_cells;                 /* cells of the population                       */
+    const int32_t *cells;                   /* host: their cell indices (-1: zeros); NULL: all */
+    int32_t        low_coverage_threshold;  /* cells with cov < this are "low" (0: none)     */
+} mgp_variant_job;
+/* Caller-owned host arrays; [mito_len][4] unless noted (bases A, C, G, T). */
+typedef struct mgp_variant_moments {
+    uint64_t *n_det;    /* cells with f + r > 0                                */
+    uint64_t *n_conf;   /* cells with f >= 2 and r >= 2                        */
+    uint64_t *s_total;  /* sum of f + r                                        */
+    uint64_t *s_cov;    /* [mito_len]: sum of cov                              */
+    uint64_t *m;        /* cells with f > 0; the five sums below are over them */
+    uint64_t *sf;       /* sum f   */
+    uint64_t *sr;       /* sum r   */
+    uint64_t *sff;      /* sum f^2 */
+    uint64_t *srr;      /* sum r^2 */
+    uint64_t *sfr;      /* sum f r */
+    uint64_t *n_low;    /* [mito_len]: cells with cov < low_coverage_threshold */
+    double   *s_af;     /* sum of af over the cells that are not low (summed in a fixed
+                           order: the same rows give the same bytes)           */
+} mgp_variant_moments;
+/* Pass 1 (implies mgp_sync; after mgp_run and before mgp_close, like mgp_txt_gz_run). */
+int  mgp_variant_moments_run(mgp_ctx *ctx, const mgp_variant_job *job, mgp_variant_moments *out);
+/* Pass 2: out_dev2 [mito_len][4] = the sum over the cells that are not low of
+ * (af - mean_af[p][b])^2, mean_af [mito_len][4] from the host (never sum x^2 - (sum x)^2 / n). */
+int  mgp_variant_dev2_run(mgp_ctx *ctx, const mgp_variant_job *job, const double *mean_af, double *out_dev2);
+/* The heteroplasmy matrix: out [n_var][n_cells] = (f + r) / cov of base[v] (0..3) at
+ * pos[v] (0-based) for each cell of the population, 0 where cov < min_coverage or cov == 0
+ * (low_coverage_threshold is not used). At most 2^29 values per call. */
+int  mgp_allele_freq_run(mgp_ctx *ctx, const mgp_variant_job *job, int64_t n_var, const int32_t *pos,
+                         const int32_t *base, int32_t min_coverage, double *out);
+/* The same three from caller-supplied u32 rows (counts [n_rows][mito_len][8], depth
+ * [n_rows][mito_len]) on `device`, no engine context, as mgp_txt_gz_rows. */
+int  mgp_variant_moments_rows(int device, const uint32_t *counts, const uint32_t *depth, int32_t n_rows,
+                              int32_t mito_len, const mgp_variant_job *job, mgp_variant_moments *out);
+int  mgp_variant_dev2_rows(int device, const uint32_t *counts, const uint32_t *depth, int32_t n_rows,
+                           int32_t mito_len, const mgp_variant_job *job, const double *mean_af, double *out_dev2);
+int  mgp_allele_freq_rows(int device, const uint32_t *counts, const uint32_t *depth, int32_t n_rows,
+                          int32_t mito_len, const mgp_variant_job *job, int64_t n_var, const int32_t *pos,
+                          const int32_t *base, int32_t min_coverage, double *out);
 /* Position windows of the pileup (the `wide` flags' second dimension). */
 int  mgp_windows(mgp_ctx *ctx, int32_t *n_windows, int32_t *window_width);
 /* Wait until the H2D copies of every batch pushed so far have completed: the caller may

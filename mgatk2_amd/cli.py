@@ -2,7 +2,8 @@
 
 Same commands, option names, short flags and defaults as the reference, so a
 reference command line runs unchanged (``python -m mgatk2_amd run -i ...``).
-Added: ``--device`` (HIP device ordinal for the engine).
+Added: ``--device`` (HIP device ordinal for the engine) and ``--variants`` with its
+``--variant-*`` thresholds (variant calling from the device's rows, variants/ in the output).
 Not carried over: ``hardmask-fasta`` (FASTA masking utility, outside the hot path).
 """
 
@@ -29,6 +30,37 @@ DEDUP_CHOICES = ["alignment_and_fragment_length", "alignment_start", "none"]
 # ---------------------------------------------------------------------------
 # options (options.py:6-306)
 # ---------------------------------------------------------------------------
+def _variant_options(f):
+    """--variants and its thresholds (after every reference option)."""
+    opts = [
+        click.option("--variants", "call_variants", is_flag=True,
+                     help="Call variants on the device: variants/variant_stats.tsv and the heteroplasmy matrix"),
+        click.option("--variant-min-cells", default=5, type=int, show_default=True,
+                     help="Minimum cells with >= 2 reads of the allele on each strand"),
+        click.option("--variant-min-strand-cor", default=0.65, type=float, show_default=True,
+                     help="Minimum strand correlation"),
+        click.option("--variant-min-vmr", default=0.01, type=float, show_default=True,
+                     help="Variance-to-mean ratio a variant must exceed"),
+        click.option("--variant-stabilize", is_flag=True,
+                     help="Variance stabilisation: low-coverage cells take the bulk allele frequency"),
+        click.option("--variant-low-coverage", default=10, type=int, show_default=True,
+                     help="Depth below which a cell is low-coverage (with --variant-stabilize)"),
+        click.option("--variant-min-coverage", default=1, type=int, show_default=True,
+                     help="Depth below which the heteroplasmy matrix is 0"),
+    ]
+    for o in reversed(opts):
+        f = o(f)
+    return f
+
+
+def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
+                  variant_low_coverage, variant_min_coverage) -> dict:
+    return dict(call_variants=call_variants, variant_min_cells=variant_min_cells,
+                variant_min_strand_cor=variant_min_strand_cor, variant_min_vmr=variant_min_vmr,
+                variant_stabilize=variant_stabilize, variant_low_coverage=variant_low_coverage,
+                variant_min_coverage=variant_min_coverage)
+
+
 def _options(defaults: dict, helps: dict | None = None):
     d = defaults
 
@@ -185,7 +217,7 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
                          verbose, batch_size, max_memory, base_qual, min_mapq, min_reads, max_strand_bias,
                          min_distance_from_end, dedup_mode, output_format, sequential, dry_run=False,
                          original_bam_path=None, report_title=None, report_subtitle=None, working_directory=None,
-                         device=0, devices=None) -> int:
+                         device=0, devices=None, variant_args: dict | None = None) -> int:
     """cli/utils.py:124-289: returns 0 on success, 1 on a handled error."""
     from .pipeline import run_pipeline
     from .utils import validate_bam_file, validate_barcode_file
@@ -225,6 +257,10 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
         logger.info("  Output format:          %s", output_format)
         logger.info("  Barcodes:               %s", _count_barcodes(barcode_file))
         logger.info("  HIP device:             %s", device)
+        if variant_args and variant_args.get("call_variants"):
+            logger.info("  Variant calling:        min cells %s, min strand cor %s, min vmr %s",
+                        variant_args["variant_min_cells"], variant_args["variant_min_strand_cor"],
+                        variant_args["variant_min_vmr"])
         if dry_run:
             return 0
         if report_title is None:
@@ -242,6 +278,8 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
         )
         if max_memory is not None:
             run_args["max_memory_gb"] = max_memory
+        if variant_args and variant_args.get("call_variants"):
+            run_args.update(variant_args)
         run_pipeline(**run_args)
         return 0
     except InvalidInputError as e:
@@ -275,9 +313,10 @@ def cli():
 
 @cli.command()
 @_options(RUN_DEFAULTS)
+@_variant_options
 def run(bam_path, mito_genome, barcode_file, barcode_tag, min_barcode_reads, output_dir, ncores, verbose, batch_size,
         max_memory, base_qual, min_mapq, min_reads, max_strand_bias, min_distance_from_end, dedup_mode,
-        output_format, dry_run, device, devices):
+        output_format, dry_run, device, devices, **variant_kw):
     """Run mgatk2 with optimised defaults"""
     try:
         rc = run_pipeline_command(
@@ -285,7 +324,7 @@ def run(bam_path, mito_genome, barcode_file, barcode_tag, min_barcode_reads, out
             batch_size, max_memory, base_qual, min_mapq, min_reads, max_strand_bias, min_distance_from_end,
             dedup_mode, output_format, ncores == 1, dry_run=dry_run, original_bam_path=bam_path,
             report_title=get_10x_parent_directory_name(bam_path), report_subtitle="mgatk2 output analysis",
-            working_directory=os.getcwd(), device=device, devices=devices)
+            working_directory=os.getcwd(), device=device, devices=devices, variant_args=_variant_args(**variant_kw))
     except KeyboardInterrupt:
         raise SystemExit(130) from None
     if rc:
@@ -294,14 +333,16 @@ def run(bam_path, mito_genome, barcode_file, barcode_tag, min_barcode_reads, out
 
 @cli.command()
 @_options(TENX_DEFAULTS)
+@_variant_options
 def tenx(bam_path, mito_genome, barcode_file, barcode_tag, min_barcode_reads, output_dir, ncores, verbose, batch_size,
          max_memory, base_qual, min_mapq, min_reads, max_strand_bias, min_distance_from_end, dedup_mode,
-         output_format, dry_run, device, devices):
+         output_format, dry_run, device, devices, **variant_kw):
     """Run mgatk2 with original mgatk package behaviour"""
     rc = run_pipeline_command(
         bam_path, output_dir, barcode_file, barcode_tag, min_barcode_reads, mito_genome, ncores, verbose,
         batch_size, max_memory, base_qual, min_mapq, min_reads, max_strand_bias, min_distance_from_end, dedup_mode,
-        output_format, ncores == 1, dry_run=dry_run, device=device, devices=devices)
+        output_format, ncores == 1, dry_run=dry_run, device=device, devices=devices,
+        variant_args=_variant_args(**variant_kw))
     if rc:
         raise SystemExit(rc)
 
@@ -324,8 +365,9 @@ def tenx(bam_path, mito_genome, barcode_file, barcode_tag, min_barcode_reads, ou
               default="hdf5", show_default=True)
 @click.option("--dry-run", is_flag=True)
 @click.option("--device", "device", default=0, type=int, show_default=True)
+@_variant_options
 def call(bam_path, mito_genome, output_dir, ncores, verbose, max_memory, base_qual, min_mapq, max_strand_bias,
-         min_distance_from_end, dedup_mode, output_format, dry_run, device):
+         min_distance_from_end, dedup_mode, output_format, dry_run, device, **variant_kw):
     """Run mgatk2 and treat each bam file as a single cell (commands/call.py)"""
     bam_files = sorted(Path(bam_path).glob("*.bam"))
     if not bam_files:
@@ -341,7 +383,7 @@ def call(bam_path, mito_genome, output_dir, ncores, verbose, max_memory, base_qu
         logger.info(f"[{i}/{len(bam_files)}] Processing: {bam_file.name} -> {out}")
         run_pipeline_command(str(bam_file), str(out), None, "CB", 10, mito_chr, ncores, verbose, 1, max_memory,
                              base_qual, min_mapq, 0, max_strand_bias, min_distance_from_end, dedup_mode, output_format,
-                             ncores == 1, dry_run=False, device=device)
+                             ncores == 1, dry_run=False, device=device, variant_args=_variant_args(**variant_kw))
     logger.info("Analysis completed for all %s BAM files", len(bam_files))
 
 

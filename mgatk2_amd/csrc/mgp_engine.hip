@@ -34,12 +34,14 @@
 #include <type_traits>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/mgpileup.h"
 #include "mgp_kernels.h"
 #include "mgp_txtgz.h"
+#include "mgp_variants.h"
 
 using namespace mgp;
 
@@ -124,6 +126,12 @@ struct TxtState {
 struct H5State {
     DevBuf coc, raw, tok, out, out_off, chunk_bytes, dst_off, packed, sums, prof;
     uint64_t total = 0;
+};
+
+// mgp_variant_* / mgp_allele_freq_*: the variant reductions' buffers (mgp_variants.hip)
+struct VarState {
+    DevBuf cells, acc, part, f64, mu, pos, base, bad, out;
+    DevBuf rows_c, rows_d;  // (the *_rows forms: the caller's u32 rows)
 };
 
 enum Stage { ST_HIST, ST_SCAN, ST_GROUP_A, ST_GROUP_B, ST_PILEUP, ST_GATE, ST_MEDIAN, ST_TALLY, ST_COMM, ST_N };
@@ -246,6 +254,7 @@ struct mgp_ctx {
 
     TxtState txt;  // mgp_txt_gz
     H5State h5;    // mgp_h5_tiles
+    VarState var;  // mgp_variant_*, mgp_allele_freq_*
 };
 
 // ---------------------------------------------------------------------------
@@ -5048,6 +5057,232 @@ int mgp_txt_gz_rows(int device, const uint32_t* counts, const uint32_t* depth, i
     }
     (void)hipStreamDestroy(s);
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// mgp_variant_* / mgp_allele_freq_*: variant statistics and heteroplasmy from the count
+// rows (identify_variants / calculate_allele_freq, R/mgatk2_functions.R:282-372)
+// ---------------------------------------------------------------------------
+// MGP_VAR_PROF: the kernels' device time between two events of the call's stream, to stderr
+struct VarProf {
+    hipStream_t s;
+    hipEvent_t a = nullptr, b = nullptr;
+    explicit VarProf(hipStream_t st) : s(st) {
+        if (!std::getenv("MGP_VAR_PROF")) return;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
+        (void)hipEventRecord(a, s);
+    }
+    void stop() {
+        if (a && b) (void)hipEventRecord(b, s);
+    }
+    // (after the stream is synchronised)
+    void report(const char* who, const char* what, int64_t n, int64_t m) {
+        float ms = 0;
+        if (a && b && hipEventElapsedTime(&ms, a, b) == hipSuccess)
+            std::fprintf(stderr, "[%s] %lld x %lld %s: kernels %.3f ms\n", who, (long long)n, (long long)m, what, ms);
+    }
+    ~VarProf() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+// the job's population on the device: *cells = its list (null: rows 0..n-1), *n its size
+static int var_population(VarState& st, hipStream_t s, int32_t n_rows, const mgp_variant_job* job, const char* who,
+                          const int32_t** cells, int64_t* n) {
+    if (!job || job->low_coverage_threshold < 0 || (job->cells && job->n_cells < 0))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    *n = job->cells ? job->n_cells : (int64_t)n_rows;
+    *cells = nullptr;
+    if (*n > variants::kMaxCells)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 65536 cells in one call (the exactness bound of "
+                                                         "the u64 moments); split the population and add the moments");
+    if (!job->cells) return MGP_OK;
+    for (int64_t k = 0; k < *n; ++k)
+        if (job->cells[k] < -1 || job->cells[k] >= n_rows)
+            return set_err(MGP_E_INVALID, std::string(who) + ": cell out of range");
+    MGP_TRY(st.cells.ensure((size_t)std::max<int64_t>(*n, 1) * 4));
+    if (*n) HIP_TRY(hipMemcpyAsync(st.cells.p, job->cells, (size_t)*n * 4, hipMemcpyHostToDevice, s));
+    *cells = st.cells.as<int32_t>();
+    return MGP_OK;
+}
+
+static int var_moments(VarState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const mgp_variant_job* job,
+                       mgp_variant_moments* out) {
+    using namespace variants;
+    const char* who = "mgp_variant_moments";
+    if (!out || !out->n_det || !out->n_conf || !out->s_total || !out->s_cov || !out->m || !out->sf || !out->sr ||
+        !out->sff || !out->srr || !out->sfr || !out->n_low || !out->s_af)
+        return set_err(MGP_E_INVALID, std::string(who) + ": null output array");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st, s, n_rows, job, who, &cells, &n));
+    const size_t L = (size_t)rows.L, plane = L * 4;
+    MGP_TRY(st.acc.ensure(acc_words(rows.L) * 8));
+    MGP_TRY(st.part.ensure((size_t)slabs(n) * plane * 8));
+    MGP_TRY(st.f64.ensure(plane * 8));
+    MGP_TRY(st.bad.ensure(4));
+    VarProf prof(s);
+    if (moments(rows, cells, n, (uint32_t)job->low_coverage_threshold, st.acc.as<unsigned long long>(),
+                st.part.as<double>(), st.f64.as<double>(), st.bad.as<uint32_t>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "cells x positions", n, rows.L);
+    if (bad)
+        return set_err(MGP_E_INVALID, std::string(who) + ": a fwd or rev count of the population is 2^24 or more "
+                                                         "(the exactness bound of the u64 moments)");
+    uint64_t* dst[F_N] = {out->n_det, out->n_conf, out->s_total, out->m, out->sf, out->sr, out->sff, out->srr, out->sfr};
+    const uint64_t* acc = st.acc.as<uint64_t>();
+    for (int k = 0; k < F_N; ++k) HIP_TRY(hipMemcpyAsync(dst[k], acc + k * plane, plane * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->s_cov, acc + acc_scov(rows.L), L * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->n_low, acc + acc_nlow(rows.L), L * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->s_af, st.f64.p, plane * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MGP_OK;
+}
+
+static int var_dev2(VarState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const mgp_variant_job* job,
+                    const double* mean_af, double* out_dev2) {
+    using namespace variants;
+    const char* who = "mgp_variant_dev2";
+    if (!mean_af || !out_dev2) return set_err(MGP_E_INVALID, std::string(who) + ": null mean_af / out_dev2");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st, s, n_rows, job, who, &cells, &n));
+    const size_t plane = (size_t)rows.L * 4;
+    MGP_TRY(st.part.ensure((size_t)slabs(n) * plane * 8));
+    MGP_TRY(st.f64.ensure(plane * 8));
+    MGP_TRY(st.mu.ensure(plane * 8));
+    HIP_TRY(hipMemcpyAsync(st.mu.p, mean_af, plane * 8, hipMemcpyHostToDevice, s));
+    VarProf prof(s);
+    if (dev2(rows, cells, n, (uint32_t)job->low_coverage_threshold, st.mu.as<double>(), st.part.as<double>(),
+             st.f64.as<double>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    HIP_TRY(hipMemcpyAsync(out_dev2, st.f64.p, plane * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "cells x positions", n, rows.L);
+    return MGP_OK;
+}
+
+static int var_allele_freq(VarState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows,
+                           const mgp_variant_job* job, int64_t n_var, const int32_t* pos, const int32_t* base,
+                           int32_t min_coverage, double* out) {
+    const char* who = "mgp_allele_freq";
+    if (n_var < 0 || min_coverage < 0 || (n_var > 0 && (!pos || !base)))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st, s, n_rows, job, who, &cells, &n));
+    for (int64_t v = 0; v < n_var; ++v)
+        if (pos[v] < 0 || pos[v] >= rows.L || base[v] < 0 || base[v] > 3)
+            return set_err(MGP_E_INVALID, std::string(who) + ": variant position or base out of range");
+    if (n == 0 || n_var == 0) return MGP_OK;
+    if (!out) return set_err(MGP_E_INVALID, std::string(who) + ": null output");
+    if (n_var > ((int64_t)1 << 29) / n)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^29 values in one call; split the variants");
+    const size_t vals = (size_t)n_var * (size_t)n;
+    MGP_TRY(st.pos.ensure((size_t)n_var * 4));
+    MGP_TRY(st.base.ensure((size_t)n_var * 4));
+    MGP_TRY(st.out.ensure(vals * 8));
+    HIP_TRY(hipMemcpyAsync(st.pos.p, pos, (size_t)n_var * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(st.base.p, base, (size_t)n_var * 4, hipMemcpyHostToDevice, s));
+    VarProf prof(s);
+    if (variants::gather(rows, cells, n, st.pos.as<int32_t>(), st.base.as<int32_t>(), n_var, (uint32_t)min_coverage,
+                         st.out.as<double>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    HIP_TRY(hipMemcpyAsync(out, st.out.p, vals * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "variants x cells", n_var, n);
+    return MGP_OK;
+}
+
+// the run's rows of a context (after mgp_run)
+static int var_ctx_rows(mgp_ctx* ctx, const char* who, txtgz::Rows* rows) {
+    if (!ctx) return set_err(MGP_E_INVALID, "null ctx");
+    MGP_TRY(mgp_sync(ctx));
+    HIP_TRY(hipSetDevice(ctx->dev));
+    if (!ctx->ran) return set_err(MGP_E_STATE, std::string(who) + ": no run to read (mgp_run first)");
+    const Geom& g = ctx->g;
+    *rows = txtgz::Rows{reinterpret_cast<const uint4*>(ctx->counts16.p), ctx->depth16.as<uint16_t>(),
+                        ctx->wide.as<uint8_t>(), ctx->counts.as<uint32_t>(), ctx->depth.as<uint32_t>(), g.L, g.W, g.nwin};
+    return MGP_OK;
+}
+
+int mgp_variant_moments_run(mgp_ctx* ctx, const mgp_variant_job* job, mgp_variant_moments* out) {
+    txtgz::Rows rows{};
+    MGP_TRY(var_ctx_rows(ctx, "mgp_variant_moments_run", &rows));
+    return var_moments(ctx->var, ctx->s_comp, rows, ctx->g.nc, job, out);
+}
+
+int mgp_variant_dev2_run(mgp_ctx* ctx, const mgp_variant_job* job, const double* mean_af, double* out_dev2) {
+    txtgz::Rows rows{};
+    MGP_TRY(var_ctx_rows(ctx, "mgp_variant_dev2_run", &rows));
+    return var_dev2(ctx->var, ctx->s_comp, rows, ctx->g.nc, job, mean_af, out_dev2);
+}
+
+int mgp_allele_freq_run(mgp_ctx* ctx, const mgp_variant_job* job, int64_t n_var, const int32_t* pos,
+                        const int32_t* base, int32_t min_coverage, double* out) {
+    txtgz::Rows rows{};
+    MGP_TRY(var_ctx_rows(ctx, "mgp_allele_freq_run", &rows));
+    return var_allele_freq(ctx->var, ctx->s_comp, rows, ctx->g.nc, job, n_var, pos, base, min_coverage, out);
+}
+
+// the *_rows forms: the caller's u32 rows uploaded, `fn(state, stream, rows)` run on them
+static int var_on_rows(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                       const char* who, const std::function<int(VarState&, hipStream_t, const txtgz::Rows&)>& fn) {
+    if (n_rows < 0 || mito_len <= 0 || (n_rows > 0 && (!counts || !depth)))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    int rc = MGP_OK;
+    {
+        VarState st;
+        const size_t npos = (size_t)n_rows * (size_t)mito_len;
+        rc = st.rows_c.ensure(npos * 32 + 64);
+        if (rc == MGP_OK) rc = st.rows_d.ensure(npos * 4 + 64);
+        if (rc == MGP_OK && npos) {
+            if (hipMemcpy(st.rows_c.p, counts, npos * 32, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(st.rows_d.p, depth, npos * 4, hipMemcpyHostToDevice) != hipSuccess)
+                rc = set_err(MGP_E_HIP, std::string(who) + ": upload failed");
+        }
+        txtgz::Rows rows{nullptr, nullptr, nullptr, st.rows_c.as<uint32_t>(), st.rows_d.as<uint32_t>(), mito_len,
+                         mito_len, 1};
+        if (rc == MGP_OK) rc = fn(st, s, rows);
+        (void)hipStreamSynchronize(s);
+    }
+    (void)hipStreamDestroy(s);
+    return rc;
+}
+
+int mgp_variant_moments_rows(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                             const mgp_variant_job* job, mgp_variant_moments* out) {
+    return var_on_rows(device, counts, depth, n_rows, mito_len, "mgp_variant_moments_rows",
+                       [&](VarState& st, hipStream_t s, const txtgz::Rows& rows) {
+                           return var_moments(st, s, rows, n_rows, job, out);
+                       });
+}
+
+int mgp_variant_dev2_rows(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                          const mgp_variant_job* job, const double* mean_af, double* out_dev2) {
+    return var_on_rows(device, counts, depth, n_rows, mito_len, "mgp_variant_dev2_rows",
+                       [&](VarState& st, hipStream_t s, const txtgz::Rows& rows) {
+                           return var_dev2(st, s, rows, n_rows, job, mean_af, out_dev2);
+                       });
+}
+
+int mgp_allele_freq_rows(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                         const mgp_variant_job* job, int64_t n_var, const int32_t* pos, const int32_t* base,
+                         int32_t min_coverage, double* out) {
+    return var_on_rows(device, counts, depth, n_rows, mito_len, "mgp_allele_freq_rows",
+                       [&](VarState& st, hipStream_t s, const txtgz::Rows& rows) {
+                           return var_allele_freq(st, s, rows, n_rows, job, n_var, pos, base, min_coverage, out);
+                       });
 }
 
 }  // extern "C"

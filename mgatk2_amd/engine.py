@@ -40,7 +40,8 @@ ABI_SYMBOLS = (
     "mgp_download_inputs", "mgp_set_stage_timing", "mgp_fetch_cells", "mgp_fetch_rows16", "mgp_windows",
     "mgp_stream_info", "mgp_set_streaming", "mgp_set_rows16_target", "mgp_copy_wait", "mgp_set_cell_range",
     "mgp_push_batch16", "mgp_txt_gz_run", "mgp_txt_gz_fetch", "mgp_txt_gz_rows", "mgp_set_rows_target",
-    "mgp_h5_tiles_run", "mgp_h5_tiles_fetch",
+    "mgp_h5_tiles_run", "mgp_h5_tiles_fetch", "mgp_variant_moments_run", "mgp_variant_dev2_run",
+    "mgp_allele_freq_run", "mgp_variant_moments_rows", "mgp_variant_dev2_rows", "mgp_allele_freq_rows",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -171,6 +172,24 @@ class mgp_h5_tiles(C.Structure):
     ]
 
 
+class mgp_variant_job(C.Structure):
+    _fields_ = [
+        ("n_cells", C.c_int64),
+        ("cells", C.c_void_p),
+        ("low_coverage_threshold", C.c_int32),
+    ]
+
+
+# the arrays of mgp_variant_moments, in its order: uint64 [L, 4] except s_cov and n_low
+# (uint64 [L]) and s_af (float64 [L, 4])
+MOMENT_FIELDS = ("n_det", "n_conf", "s_total", "s_cov", "m", "sf", "sr", "sff", "srr", "sfr", "n_low", "s_af")
+MOMENT_PER_POS = ("s_cov", "n_low")
+
+
+class mgp_variant_moments(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in MOMENT_FIELDS]
+
+
 H5_PLANES = ("A_fwd", "A_rev", "C_fwd", "C_rev", "G_fwd", "G_rev", "T_fwd", "T_rev", "tn5_cuts_fwd", "tn5_cuts_rev",
              "coverage")  # the planes of mgp_h5_tiles, in its order
 
@@ -247,6 +266,16 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_h5_tiles_fetch": ([vp, vp, i64], C.c_int),
         "mgp_txt_gz_fetch": ([vp, vp, i64], C.c_int),
         "mgp_txt_gz_rows": ([C.c_int, vp, vp, i32, i32, C.POINTER(mgp_txt_gz), vp, i64, C.POINTER(i64)], C.c_int),
+        "mgp_variant_moments_run": ([vp, C.POINTER(mgp_variant_job), C.POINTER(mgp_variant_moments)], C.c_int),
+        "mgp_variant_dev2_run": ([vp, C.POINTER(mgp_variant_job), vp, vp], C.c_int),
+        "mgp_allele_freq_run": ([vp, C.POINTER(mgp_variant_job), i64, vp, vp, i32, vp], C.c_int),
+        "mgp_variant_moments_rows": (
+            [C.c_int, vp, vp, i32, i32, C.POINTER(mgp_variant_job), C.POINTER(mgp_variant_moments)], C.c_int
+        ),
+        "mgp_variant_dev2_rows": ([C.c_int, vp, vp, i32, i32, C.POINTER(mgp_variant_job), vp, vp], C.c_int),
+        "mgp_allele_freq_rows": (
+            [C.c_int, vp, vp, i32, i32, C.POINTER(mgp_variant_job), i64, vp, vp, i32, vp], C.c_int
+        ),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -481,6 +510,96 @@ def txt_gz_rows(counts: np.ndarray, depth: np.ndarray, cells, names: list[str], 
     return TxtMembers(out[:int(tot.value)], mb, tb)
 
 
+VARIANT_MAX_CELLS = 1 << 16  # cells of one mgp_variant_* call (the u64 moments' exactness bound)
+ALLELE_FREQ_MAX_VALUES = 1 << 29  # values of one mgp_allele_freq_* call
+
+
+def alloc_moments(L: int) -> dict:
+    """Zeroed host arrays of mgp_variant_moments, by field name (MOMENT_FIELDS)."""
+    return {k: np.zeros(L if k in MOMENT_PER_POS else (L, 4), np.float64 if k == "s_af" else np.uint64)
+            for k in MOMENT_FIELDS}
+
+
+def _variant_job(cells, low_coverage_threshold: int = 0):
+    cells = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32)
+    job = mgp_variant_job(0 if cells is None else cells.shape[0], _ptr(cells), int(low_coverage_threshold))
+    return job, cells
+
+
+def _variant_list(variants):
+    """(pos int32 [n_var], base int32 [n_var]) of an iterable of (0-based position, base 0..3)."""
+    v = np.asarray(list(variants), dtype=np.int64).reshape(-1, 2)
+    return np.ascontiguousarray(v[:, 0], np.int32), np.ascontiguousarray(v[:, 1], np.int32)
+
+
+def _variant_calls(call, n_rows: int, L: int):
+    """The three reductions over one row source: call(name, *args) runs mgp_<name>_run on a
+    context or mgp_<name>_rows on caller rows."""
+
+    def moments(cells=None, low_coverage_threshold: int = 0) -> dict:
+        job, keep = _variant_job(cells, low_coverage_threshold)
+        out = alloc_moments(L)
+        call("mgp_variant_moments", C.byref(job), C.byref(mgp_variant_moments(*[_ptr(out[k]) for k in MOMENT_FIELDS])))
+        return out
+
+    def dev2(mean_af, cells=None, low_coverage_threshold: int = 0) -> np.ndarray:
+        job, keep = _variant_job(cells, low_coverage_threshold)
+        mu = np.ascontiguousarray(mean_af, np.float64)
+        if mu.shape != (L, 4):
+            raise InvalidInputError("mean_af must be [mito_len, 4]")
+        out = np.zeros((L, 4), np.float64)
+        call("mgp_variant_dev2", C.byref(job), _ptr(mu), _ptr(out))
+        return out
+
+    def allele_freq(variants, cells=None, min_coverage: int = 1) -> np.ndarray:
+        job, keep = _variant_job(cells)
+        pos, base = _variant_list(variants)
+        n = n_rows if keep is None else keep.shape[0]
+        out = np.zeros((pos.shape[0], n), np.float64)
+        step = max(1, ALLELE_FREQ_MAX_VALUES // max(1, n))
+        for a in range(0, pos.shape[0], step):
+            b = min(pos.shape[0], a + step)
+            call("mgp_allele_freq", C.byref(job), b - a, _ptr(pos[a:b]), _ptr(base[a:b]), int(min_coverage),
+                 _ptr(out[a:b]))
+        return out
+
+    return moments, dev2, allele_freq
+
+
+def _rows_calls(counts: np.ndarray, depth: np.ndarray, device: int):
+    lib = load_library()
+    counts = np.ascontiguousarray(counts, np.uint32)
+    depth = np.ascontiguousarray(depth, np.uint32)
+    n_rows, L = depth.shape
+    if counts.shape != (n_rows, L, 8):
+        raise InvalidInputError("counts must be [n, L, 8]")
+
+    def call(name, *args):
+        _ck(getattr(lib, name + "_rows")(int(device), _ptr(counts), _ptr(depth), int(n_rows), int(L), *args),
+            name + "_rows")
+
+    return _variant_calls(call, n_rows, L)
+
+
+def variant_moments_rows(counts: np.ndarray, depth: np.ndarray, cells=None, low_coverage_threshold: int = 0,
+                         device: int = 0) -> dict:
+    """mgp_variant_moments_rows: Engine.variant_moments on caller-supplied u32 rows (counts
+    [n, L, 8], depth [n, L]), no engine context."""
+    return _rows_calls(counts, depth, device)[0](cells, low_coverage_threshold)
+
+
+def variant_dev2_rows(counts: np.ndarray, depth: np.ndarray, mean_af, cells=None, low_coverage_threshold: int = 0,
+                      device: int = 0) -> np.ndarray:
+    """mgp_variant_dev2_rows: Engine.variant_dev2 on caller-supplied u32 rows."""
+    return _rows_calls(counts, depth, device)[1](mean_af, cells, low_coverage_threshold)
+
+
+def allele_freq_rows(counts: np.ndarray, depth: np.ndarray, variants, cells=None, min_coverage: int = 1,
+                     device: int = 0) -> np.ndarray:
+    """mgp_allele_freq_rows: Engine.allele_freq on caller-supplied u32 rows."""
+    return _rows_calls(counts, depth, device)[2](variants, cells, min_coverage)
+
+
 class Engine:
     """One device context (one GPU). Not thread-safe."""
 
@@ -681,6 +800,32 @@ class Engine:
         if sums is not None:
             sums.update(coverage=acc[0], tn5_fwd=acc[1], tn5_rev=acc[2])
         return {p: [b for row in grid[p] for b in row] for p in H5_PLANES}
+
+    def _variant_calls(self):
+        def call(name, *args):
+            _ck(getattr(self.lib, name + "_run")(self._h, *args), name + "_run")
+
+        return _variant_calls(call, self.cfg.n_cells, self.cfg.mito_len)
+
+    def variant_moments(self, cells=None, low_coverage_threshold: int = 0) -> dict:
+        """mgp_variant_moments_run (pass 1 of the variant statistics, after run()): the
+        per-(position, base) moments over the population `cells` (context cell indices in
+        order, -1 = an all-zero row; None = every cell) from the run's rows in HBM, as a
+        dict of MOMENT_FIELDS arrays: exact uint64 sums, and s_af, the fp64 sum of the
+        allele frequencies of the cells with depth >= low_coverage_threshold (0: all).
+        At most VARIANT_MAX_CELLS cells per call, every count below 2^24."""
+        return self._variant_calls()[0](cells, low_coverage_threshold)
+
+    def variant_dev2(self, mean_af, cells=None, low_coverage_threshold: int = 0) -> np.ndarray:
+        """mgp_variant_dev2_run (pass 2): [L, 4] sums of (af - mean_af)^2 over the cells of
+        the population that are not low."""
+        return self._variant_calls()[1](mean_af, cells, low_coverage_threshold)
+
+    def allele_freq(self, variants, cells=None, min_coverage: int = 1) -> np.ndarray:
+        """mgp_allele_freq_run: the heteroplasmy matrix [n_variants, n_cells] of `variants`
+        ((0-based position, base 0..3) pairs) over the population: (fwd + rev) / depth
+        where depth >= min_coverage, else 0."""
+        return self._variant_calls()[2](variants, cells, min_coverage)
 
     def windows(self) -> tuple[int, int]:
         nw, w = C.c_int32(), C.c_int32()

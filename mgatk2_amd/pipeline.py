@@ -88,6 +88,13 @@ class MtDNAPipeline:
         device: int = 0,
         devices: list[int] | None = None,
         stream: bool | None = None,
+        call_variants: bool = False,
+        variant_min_cells: int = 5,
+        variant_min_strand_cor: float = 0.65,
+        variant_min_vmr: float = 0.01,
+        variant_stabilize: bool = False,
+        variant_low_coverage: int = 10,
+        variant_min_coverage: int = 1,
     ):
         self.bam_path = Path(bam_path)
         # streamed ingest (default; MGP_STREAM=0 decodes the whole chrM set first)
@@ -104,6 +111,11 @@ class MtDNAPipeline:
         self.working_directory = working_directory
         self.device = device
         self.devices = list(devices) if devices else [device]
+        # variant calling from the devices' rows (off unless asked for): variants/ in the output
+        self.call_variants = bool(call_variants)
+        self.variant_options = dict(min_cells=variant_min_cells, min_strand_cor=variant_min_strand_cor,
+                                    min_vmr=variant_min_vmr, stabilize_variance=bool(variant_stabilize),
+                                    low_coverage_threshold=variant_low_coverage, min_coverage=variant_min_coverage)
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -151,6 +163,8 @@ class MtDNAPipeline:
         else:
             # the HDF5 chunks are deflated on the device at the end of the run (mgp_h5_tiles)
             processor.enable_device_h5(self.barcode_list)
+        if self.call_variants:
+            processor.enable_variants(**self.variant_options)
         if self.stream:
             # one pass: batches decoded on a producer thread, each pushed to the device as
             # it is ready, the windows piled as their reads arrive (readers.py:84-93)
@@ -204,6 +218,12 @@ class MtDNAPipeline:
         meta = QCCalculator(self.config).collect_run_metadata(
             str(self.bam_path), str(self.output_dir), n_cells_input, len(cell_results))
         write_run_summary(meta, qc_dir / "summary.txt")
+        if self.call_variants and getattr(res, "variants", None) is not None:
+            from .analysis.variants import write_variant_outputs
+
+            write_variant_outputs(res.variants, res.allele_freq, self.barcode_list, self.output_dir,
+                                  self.output_format)
+            logger.info("%d variants called", len(res.variants))
         t3 = time.time()
         gc.collect()
 
@@ -264,9 +284,18 @@ def run_pipeline(
     working_directory: str | None = None,
     device: int = 0,
     devices: list[int] | None = None,
+    call_variants: bool = False,
+    variant_min_cells: int = 5,
+    variant_min_strand_cor: float = 0.65,
+    variant_min_vmr: float = 0.01,
+    variant_stabilize: bool = False,
+    variant_low_coverage: int = 10,
+    variant_min_coverage: int = 1,
 ) -> dict[str, Any]:
     """pipeline.py:183-269. ``min_distance_from_end`` is accepted and, as in the
-    reference, not passed on (the engine uses 5)."""
+    reference, not passed on (the engine uses 5). ``call_variants``
+    (not in the reference's pipeline: its R step on counts.h5) writes variants/ with
+    mgatk's customary thresholds as defaults."""
     barcode_metadata = None
     if barcode_file is None:
         from .file_io.barcode_extraction import extract_barcodes_from_bam
@@ -301,6 +330,9 @@ def run_pipeline(
         bam_path=bam_path, barcodes=barcodes, output_dir=Path(output_dir), config=config,
         output_format=output_format, barcode_metadata=barcode_metadata, sample_name=sample_name,
         report_title=report_title, report_subtitle=report_subtitle, working_directory=working_directory,
-        device=device, devices=devices,
+        device=device, devices=devices, call_variants=call_variants, variant_min_cells=variant_min_cells,
+        variant_min_strand_cor=variant_min_strand_cor, variant_min_vmr=variant_min_vmr,
+        variant_stabilize=variant_stabilize, variant_low_coverage=variant_low_coverage,
+        variant_min_coverage=variant_min_coverage,
     )
     return pipeline.run()

@@ -113,6 +113,7 @@ class CellProcessor:
         self.last_timing: dict = {}
         self.txt_out = None
         self.h5_out = None
+        self.variants_opt: dict | None = None
 
     # txt output on the device ----------------------------------------------
     def enable_device_txt(self, prefix, names: list[str]):
@@ -131,6 +132,32 @@ class CellProcessor:
         IncrementalHDF5Writer.finalize writes instead of deflating the planes on the host.
         `names`: the writer's barcodes (its columns). MGP_H5_DEVICE=0 keeps the host deflate."""
         self.h5_out = list(names)
+
+    def enable_variants(self, min_cells: int = 0, min_strand_cor: float = 0, min_vmr: float = 0,
+                        stabilize_variance: bool = False, low_coverage_threshold: int = 10, min_coverage: int = 1):
+        """Call variants from the devices' rows before their contexts close (mgp_variant_*,
+        mgp_allele_freq_*; analysis/variants.py): the run's result then carries `variants`,
+        the table of identify_variants over every cell of the run (cells that did not pass
+        count as all-zero rows, the zero columns of counts.h5), and `allele_freq`, the
+        heteroplasmy matrix [n_variants, n_cells] of the variants that pass. The defaults
+        are R's (no filtering)."""
+        self.variants_opt = dict(min_cells=min_cells, min_strand_cor=min_strand_cor, min_vmr=min_vmr,
+                                 stabilize_variance=stabilize_variance,
+                                 low_coverage_threshold=low_coverage_threshold, min_coverage=min_coverage)
+
+    def _call_variants(self, res: EngineResult, parts: list) -> float:
+        """Pass 1 on every part (the devices concurrently), the host merge, pass 2, the
+        table, then the matrix of the passing variants, each part filling its own columns;
+        parts = [(engine, lo, hi)]. Returns the seconds spent."""
+        from ..analysis.variants import run_variants
+        from ..file_io.writers import ref_alleles
+
+        t0 = time.perf_counter()
+        n_cells = int(res.passed.shape[0])
+        pop = np.where(res.passed.astype(bool), np.arange(n_cells, dtype=np.int64), -1)
+        vr = run_variants(parts, ref_alleles(res.ref_tally), cells=pop, **self.variants_opt)
+        res.variants, res.allele_freq, res.variant_seconds = vr.table, vr.allele_freq, vr.seconds
+        return time.perf_counter() - t0
 
     def _h5_device_on(self) -> bool:
         return self.h5_out is not None and os.environ.get("MGP_H5_DEVICE", "1") != "0"
@@ -303,11 +330,14 @@ class CellProcessor:
             self.last_stats = eng.kernel_times()
             t_txt = self._write_txt(res, [(eng, 0, n_cells)]) if self._txt_device_on() else 0.0
             t_h5 = self._write_h5(res, [(eng, 0, n_cells)]) if self._h5_device_on() else 0.0
+            t_var = self._call_variants(res, [(eng, 0, n_cells)]) if self.variants_opt is not None else 0.0
         t4 = time.perf_counter()
         # where the engine leg goes (pipeline timings): context + allocation, H2D of
         # the batches + the run, D2H of the results, teardown
         self.last_timing = {"engine_open": t1 - t0, "engine_h2d_run": t2 - t1, "engine_d2h": t3 - t2,
-                            "engine_close": t4 - t3 - t_txt - t_h5, "txt_device": t_txt, "h5_device": t_h5}
+                            "engine_close": t4 - t3 - t_txt - t_h5 - t_var, "txt_device": t_txt, "h5_device": t_h5}
+        if self.variants_opt is not None:
+            self.last_timing["variants"] = t_var
         self.last_result = res
         return res
 
@@ -475,6 +505,7 @@ class CellProcessor:
                 _, last_streamed = eng.stream_info()
                 t_txt = self._write_txt(res, [(eng, 0, n_cells)]) if self._txt_device_on() else 0.0
                 t_h5 = self._write_h5(res, [(eng, 0, n_cells)]) if self._h5_device_on() else 0.0
+                t_var = self._call_variants(res, [(eng, 0, n_cells)]) if self.variants_opt is not None else 0.0
             finally:
                 free.put(None)
                 eng.close()
@@ -489,10 +520,12 @@ class CellProcessor:
         self.last_timing = {"stream_setup": t1 - t0, "stream_first_batch": times.get("first_batch", t1) - t0,
                             "stream_decode_end": dec_end - t0, "stream_push_end": t2 - t0,
                             "engine_tail": t3 - t2, "engine_fetch": t4 - t3,
-                            "engine_close": te - t4 - t_txt - t_h5, "txt_device": t_txt, "h5_device": t_h5,
+                            "engine_close": te - t4 - t_txt - t_h5 - t_var, "txt_device": t_txt, "h5_device": t_h5,
                             "stream_batches": n_batches, "stream_batch_reads": times["cap_reads"],
                             "streamed_run": bool(last_streamed), "rows_target": rows is not None,
                             "h2d_bytes": int(h2d)}
+        if self.variants_opt is not None:
+            self.last_timing["variants"] = t_var
         self.last_result = res
         return res
 
@@ -723,6 +756,8 @@ class CellProcessor:
                 if parts and self._txt_device_on() else 0.0
             t_h5 = self._write_h5(res, [(engines[d], lo, hi) for d, lo, hi in parts]) \
                 if parts and self._h5_device_on() else 0.0
+            t_var = self._call_variants(res, [(engines[d], lo, hi) for d, lo, hi in parts]) \
+                if parts and self.variants_opt is not None else 0.0
         finally:
             free.put(None)
             for eng in engines.values():
@@ -733,12 +768,14 @@ class CellProcessor:
         te = time.perf_counter()
         self.last_timing = {"stream_setup": t1 - t0, "stream_first_batch": times.get("first_batch", t1) - t0,
                             "stream_decode_end": times.get("decode_end", t2) - t0, "stream_push_end": t2 - t0,
-                            "engine_tail": 0.0, "engine_fetch": t3 - t2, "engine_close": te - t3 - t_txt - t_h5,
+                            "engine_tail": 0.0, "engine_fetch": t3 - t2, "engine_close": te - t3 - t_txt - t_h5 - t_var,
                             "txt_device": t_txt, "h5_device": t_h5,
                             "stream_batches": n_batches, "stream_batch_reads": times["cap_reads"],
                             "stream_devices": len(parts), "rows_target": rows is not None, "route_s": t_route,
                             "h2d_bytes": int(sum(link_bytes.values())),
                             "cell_bounds": [lo for _, lo, _ in parts] + ([parts[-1][2]] if parts else [])}
+        if self.variants_opt is not None:
+            self.last_timing["variants"] = t_var
         self.last_result = res
         return res
 
@@ -755,18 +792,32 @@ class CellProcessor:
         b = partition_cells(reads_per_cell(soa, n_cells), len(self.devices))
         shards = [(int(lo), int(hi)) + shard_soa(soa, int(lo), int(hi)) for lo, hi in zip(b[:-1], b[1:])]
 
+        engines: list = [None] * len(self.devices)  # open until the variants are called from their rows
+
         def one(i):
             lo, hi, sub, idx = shards[i]
             ec = self.config.engine_config(hi - lo, reserve_reads=sub.n, reserve_payload=sub.payload.shape[0] + 256)
-            with Engine(ec, device=self.devices[i]) as eng:
+            eng = engines[i] = Engine(ec, device=self.devices[i])
+            try:
                 if sub.n:
                     eng.push(sub)
                 eng.run()
                 return eng.fetch_compact(), lo, hi, idx
+            finally:
+                if self.variants_opt is None:
+                    eng.close()
 
-        with ThreadPoolExecutor(len(self.devices)) as ex:
-            parts = list(ex.map(one, range(len(self.devices))))
-        res = merge_results(parts, n_cells, soa.n)
+        try:
+            with ThreadPoolExecutor(len(self.devices)) as ex:
+                parts = list(ex.map(one, range(len(self.devices))))
+            res = merge_results(parts, n_cells, soa.n)
+            if self.variants_opt is not None:
+                live = [(engines[i], lo, hi) for i, (_, lo, hi, _) in enumerate(parts) if hi > lo]
+                self.last_timing = {"variants": self._call_variants(res, live) if live else 0.0}
+        finally:
+            for eng in engines:
+                if eng is not None:
+                    eng.close()
         self.last_result = res
         return res
 
