@@ -62,7 +62,10 @@ extern "C" {
                                  mgp_h5_tiles_* (the HDF5 chunks deflated on the device);
                                  added since, additive only (the version stays 7):
                                  mgp_variant_moments_*, mgp_variant_dev2_*, mgp_allele_freq_*
-                                 (variant statistics and heteroplasmy on the device) */
+                                 (variant statistics and heteroplasmy on the device),
+                                 mgp_cell_coverage_*, mgp_position_coverage_*,
+                                 mgp_position_depth_hist_*, mgp_position_depth_next_*
+                                 (coverage QC on the device) */
 
 /* ---- return codes (0 = success) ------------------------------------------ */
 #define MGP_OK               0
@@ -639,6 +642,71 @@ int  mgp_variant_dev2_rows(int device, const uint32_t *counts, const uint32_t *d
 int  mgp_allele_freq_rows(int device, const uint32_t *counts, const uint32_t *depth, int32_t n_rows,
                           int32_t mito_len, const mgp_variant_job *job, int64_t n_var, const int32_t *pos,
                           const int32_t *base, int32_t min_coverage, double *out);
+/* Coverage QC on the device (added under ABI 7). Replaces the front half of mgatk's R
+ * workflow over counts.h5 (calculate_cell_coverage_stats, calculate_position_coverage_stats,
+ * calculate_strand_coverage_stats, calculate_transposition_stats, R/mgatk2_functions.R:138-280):
+ * dense passes over the cells x positions rows, which are still in HBM. d = the filtered
+ * depth (mgp_result.depth), f_b / r_b the fwd / rev counts of base b, t_f / t_r the Tn5 cuts
+ * (mgp_result.tn5); the engine's exact values. The population is a mgp_variant_job
+ * (low_coverage_threshold is ignored): -1 = an all-zero row, NULL = every cell, duplicates
+ * allowed. Only integers are returned, each an order-free combination (add, max, min), so
+ * the same rows give the same bytes and several calls or contexts merge on the host by
+ * adding (max_depth: max; next: min). Bounds: at most 65,536 cells per call; the two sum
+ * passes (cell_coverage, position_coverage) also need mito_len <= 65,536 and every depth
+ * and count below 2^24, otherwise MGP_E_INVALID (nothing wraps). The depth_hist and
+ * depth_next passes take any u32 depth. */
+/* Caller-owned host arrays, [n_cells] each, in population order; over all mito_len positions
+ * of the cell, zeros included. */
+typedef struct mgp_cell_coverage {
+    uint64_t *s_depth;    /* sum of d                                               */
+    uint64_t *s_depth2;   /* sum of d^2                                             */
+    uint32_t *max_depth;
+    uint32_t *n_covered;  /* positions with d > 0                                   */
+    uint32_t *n_10x;      /* positions with d >= 10                                 */
+    uint32_t *n_50x;      /* positions with d >= 50                                 */
+    uint32_t *mid_lo;     /* order statistics (mito_len - 1) / 2 and mito_len / 2   */
+    uint32_t *mid_hi;     /* of the cell's depths (0-based): their mean is the median */
+} mgp_cell_coverage;
+/* Caller-owned host arrays, [mito_len] each unless noted; over the population's cells. */
+typedef struct mgp_position_coverage {
+    uint64_t *s_depth;    /* sum of d                                               */
+    uint64_t *s_depth2;   /* sum of d^2                                             */
+    uint64_t *s_fwd;      /* sum over cells and bases of f_b                        */
+    uint64_t *s_rev;      /* sum over cells and bases of r_b                        */
+    uint64_t *s_tn5_fwd;  /* sum of t_f                                             */
+    uint64_t *s_tn5_rev;  /* sum of t_r                                             */
+    uint64_t *tally;      /* [mito_len][4]: sum of f_b + r_b (A, C, G, T)           */
+    uint32_t *n_covered;  /* cells with d > 0                                       */
+    uint32_t *n_10x;      /* cells with d >= 10                                     */
+    uint32_t *n_50x;      /* cells with d >= 50                                     */
+    uint32_t *n_tn5;      /* cells with t_f + t_r > 0                               */
+    uint32_t *max_depth;
+} mgp_position_coverage;
+/* After mgp_run and before mgp_close (imply mgp_sync), like mgp_variant_moments_run. */
+int  mgp_cell_coverage_run(mgp_ctx *ctx, const mgp_variant_job *job, mgp_cell_coverage *out);
+int  mgp_position_coverage_run(mgp_ctx *ctx, const mgp_variant_job *job, mgp_position_coverage *out);
+/* One round of the per-position radix select over the cells (the median over cells):
+ * hist [mito_len][256] = per position p, the population's cells with
+ * d >> (shift + 8) == prefix[p], counted by (d >> shift) & 255. shift is 0, 8, 16 or 24;
+ * at 24 every cell counts and prefix may be NULL. */
+int  mgp_position_depth_hist_run(mgp_ctx *ctx, const mgp_variant_job *job, int32_t shift, const uint32_t *prefix,
+                                 uint32_t *hist);
+/* n_le [mito_len] = the cells with d <= v[p]; next [mito_len] = the smallest d > v[p],
+ * 0xFFFFFFFF where there is none. */
+int  mgp_position_depth_next_run(mgp_ctx *ctx, const mgp_variant_job *job, const uint32_t *v, uint32_t *n_le,
+                                 uint32_t *next);
+/* The same four from caller-supplied u32 rows on `device`, no engine context, as
+ * mgp_variant_moments_rows: depth [n_rows][mito_len]; position_coverage also reads counts
+ * [n_rows][mito_len][8] and tn5 [n_rows][mito_len][2], the other three read depths only. */
+int  mgp_cell_coverage_rows(int device, const uint32_t *depth, int32_t n_rows, int32_t mito_len,
+                            const mgp_variant_job *job, mgp_cell_coverage *out);
+int  mgp_position_coverage_rows(int device, const uint32_t *counts, const uint32_t *tn5, const uint32_t *depth,
+                                int32_t n_rows, int32_t mito_len, const mgp_variant_job *job,
+                                mgp_position_coverage *out);
+int  mgp_position_depth_hist_rows(int device, const uint32_t *depth, int32_t n_rows, int32_t mito_len,
+                                  const mgp_variant_job *job, int32_t shift, const uint32_t *prefix, uint32_t *hist);
+int  mgp_position_depth_next_rows(int device, const uint32_t *depth, int32_t n_rows, int32_t mito_len,
+                                  const mgp_variant_job *job, const uint32_t *v, uint32_t *n_le, uint32_t *next);
 /* Position windows of the pileup (the `wide` flags' second dimension). */
 int  mgp_windows(mgp_ctx *ctx, int32_t *n_windows, int32_t *window_width);
 /* Wait until the H2D copies of every batch pushed so far have completed: the caller may

@@ -2,8 +2,10 @@
 
 Same commands, option names, short flags and defaults as the reference, so a
 reference command line runs unchanged (``python -m mgatk2_amd run -i ...``).
-Added: ``--device`` (HIP device ordinal for the engine) and ``--variants`` with its
-``--variant-*`` thresholds (variant calling from the device's rows, variants/ in the output).
+Added: ``--device`` (HIP device ordinal for the engine), ``--variants`` with its
+``--variant-*`` thresholds (variant calling from the device's rows, variants/ in the output),
+and ``--coverage-stats`` / ``--cell-min-mean-coverage`` / ``--cell-min-coverage-breadth`` /
+``--recompute-reference`` (coverage QC and the cell filter from the device's rows, coverage/).
 Not carried over: ``hardmask-fasta`` (FASTA masking utility, outside the hot path).
 """
 
@@ -47,6 +49,14 @@ def _variant_options(f):
                      help="Depth below which a cell is low-coverage (with --variant-stabilize)"),
         click.option("--variant-min-coverage", default=1, type=int, show_default=True,
                      help="Depth below which the heteroplasmy matrix is 0"),
+        click.option("--coverage-stats", is_flag=True,
+                     help="Coverage QC on the device: coverage/ with the cell, position, strand and Tn5 tables"),
+        click.option("--cell-min-mean-coverage", default=0.0, type=float, show_default=True,
+                     help="Keep cells with at least this mean depth (for the position tables and --variants)"),
+        click.option("--cell-min-coverage-breadth", default=0.0, type=float, show_default=True,
+                     help="Keep cells with at least this fraction of positions covered"),
+        click.option("--recompute-reference", is_flag=True,
+                     help="Reference alleles from the kept cells (coverage/reference_alleles.tsv; used by --variants)"),
     ]
     for o in reversed(opts):
         f = o(f)
@@ -54,11 +64,25 @@ def _variant_options(f):
 
 
 def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
-                  variant_low_coverage, variant_min_coverage) -> dict:
-    return dict(call_variants=call_variants, variant_min_cells=variant_min_cells,
-                variant_min_strand_cor=variant_min_strand_cor, variant_min_vmr=variant_min_vmr,
-                variant_stabilize=variant_stabilize, variant_low_coverage=variant_low_coverage,
-                variant_min_coverage=variant_min_coverage)
+                  variant_low_coverage, variant_min_coverage, coverage_stats=False, cell_min_mean_coverage=0.0,
+                  cell_min_coverage_breadth=0.0, recompute_reference=False) -> dict:
+    """The options run_pipeline gets beyond the reference's, each only when asked for: the
+    variant options with --variants; the four coverage options with --coverage-stats,
+    otherwise the filter thresholds and --recompute-reference that were given."""
+    out = {}
+    if call_variants:
+        out.update(call_variants=call_variants, variant_min_cells=variant_min_cells,
+                   variant_min_strand_cor=variant_min_strand_cor, variant_min_vmr=variant_min_vmr,
+                   variant_stabilize=variant_stabilize, variant_low_coverage=variant_low_coverage,
+                   variant_min_coverage=variant_min_coverage)
+    cov = dict(cell_min_mean_coverage=float(cell_min_mean_coverage),
+               cell_min_coverage_breadth=float(cell_min_coverage_breadth),
+               recompute_reference=bool(recompute_reference))
+    if coverage_stats:
+        out.update(coverage_stats=True, **cov)
+    else:
+        out.update({k: v for k, v in cov.items() if v})
+    return out
 
 
 def _options(defaults: dict, helps: dict | None = None):
@@ -261,6 +285,11 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
             logger.info("  Variant calling:        min cells %s, min strand cor %s, min vmr %s",
                         variant_args["variant_min_cells"], variant_args["variant_min_strand_cor"],
                         variant_args["variant_min_vmr"])
+        if variant_args and any(k.startswith(("coverage_", "cell_min_", "recompute_")) for k in variant_args):
+            logger.info("  Coverage QC:            tables %s, min mean coverage %s, min breadth %s, recompute reference %s",
+                        variant_args.get("coverage_stats", False), variant_args.get("cell_min_mean_coverage", 0.0),
+                        variant_args.get("cell_min_coverage_breadth", 0.0),
+                        variant_args.get("recompute_reference", False))
         if dry_run:
             return 0
         if report_title is None:
@@ -278,7 +307,7 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
         )
         if max_memory is not None:
             run_args["max_memory_gb"] = max_memory
-        if variant_args and variant_args.get("call_variants"):
+        if variant_args:
             run_args.update(variant_args)
         run_pipeline(**run_args)
         return 0

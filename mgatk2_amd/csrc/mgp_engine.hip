@@ -41,6 +41,7 @@
 #include "../../include/mgpileup.h"
 #include "mgp_kernels.h"
 #include "mgp_txtgz.h"
+#include "mgp_qc.h"
 #include "mgp_variants.h"
 
 using namespace mgp;
@@ -132,6 +133,12 @@ struct H5State {
 struct VarState {
     DevBuf cells, acc, part, f64, mu, pos, base, bad, out;
     DevBuf rows_c, rows_d;  // (the *_rows forms: the caller's u32 rows)
+};
+
+// mgp_cell_coverage_* / mgp_position_*: the coverage QC passes' buffers (mgp_qc.hip)
+struct QcState {
+    DevBuf cells, out64, out32, bad, in32, hist;
+    DevBuf rows_c, rows_d, rows_t;  // (the *_rows forms: the caller's u32 rows)
 };
 
 enum Stage { ST_HIST, ST_SCAN, ST_GROUP_A, ST_GROUP_B, ST_PILEUP, ST_GATE, ST_MEDIAN, ST_TALLY, ST_COMM, ST_N };
@@ -255,6 +262,7 @@ struct mgp_ctx {
     TxtState txt;  // mgp_txt_gz
     H5State h5;    // mgp_h5_tiles
     VarState var;  // mgp_variant_*, mgp_allele_freq_*
+    QcState qc;    // mgp_cell_coverage_*, mgp_position_*
 };
 
 // ---------------------------------------------------------------------------
@@ -5088,7 +5096,7 @@ struct VarProf {
 };
 
 // the job's population on the device: *cells = its list (null: rows 0..n-1), *n its size
-static int var_population(VarState& st, hipStream_t s, int32_t n_rows, const mgp_variant_job* job, const char* who,
+static int var_population(DevBuf& buf, hipStream_t s, int32_t n_rows, const mgp_variant_job* job, const char* who,
                           const int32_t** cells, int64_t* n) {
     if (!job || job->low_coverage_threshold < 0 || (job->cells && job->n_cells < 0))
         return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
@@ -5101,9 +5109,9 @@ static int var_population(VarState& st, hipStream_t s, int32_t n_rows, const mgp
     for (int64_t k = 0; k < *n; ++k)
         if (job->cells[k] < -1 || job->cells[k] >= n_rows)
             return set_err(MGP_E_INVALID, std::string(who) + ": cell out of range");
-    MGP_TRY(st.cells.ensure((size_t)std::max<int64_t>(*n, 1) * 4));
-    if (*n) HIP_TRY(hipMemcpyAsync(st.cells.p, job->cells, (size_t)*n * 4, hipMemcpyHostToDevice, s));
-    *cells = st.cells.as<int32_t>();
+    MGP_TRY(buf.ensure((size_t)std::max<int64_t>(*n, 1) * 4));
+    if (*n) HIP_TRY(hipMemcpyAsync(buf.p, job->cells, (size_t)*n * 4, hipMemcpyHostToDevice, s));
+    *cells = buf.as<int32_t>();
     return MGP_OK;
 }
 
@@ -5116,7 +5124,7 @@ static int var_moments(VarState& st, hipStream_t s, const txtgz::Rows& rows, int
         return set_err(MGP_E_INVALID, std::string(who) + ": null output array");
     const int32_t* cells = nullptr;
     int64_t n = 0;
-    MGP_TRY(var_population(st, s, n_rows, job, who, &cells, &n));
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
     const size_t L = (size_t)rows.L, plane = L * 4;
     MGP_TRY(st.acc.ensure(acc_words(rows.L) * 8));
     MGP_TRY(st.part.ensure((size_t)slabs(n) * plane * 8));
@@ -5151,7 +5159,7 @@ static int var_dev2(VarState& st, hipStream_t s, const txtgz::Rows& rows, int32_
     if (!mean_af || !out_dev2) return set_err(MGP_E_INVALID, std::string(who) + ": null mean_af / out_dev2");
     const int32_t* cells = nullptr;
     int64_t n = 0;
-    MGP_TRY(var_population(st, s, n_rows, job, who, &cells, &n));
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
     const size_t plane = (size_t)rows.L * 4;
     MGP_TRY(st.part.ensure((size_t)slabs(n) * plane * 8));
     MGP_TRY(st.f64.ensure(plane * 8));
@@ -5176,7 +5184,7 @@ static int var_allele_freq(VarState& st, hipStream_t s, const txtgz::Rows& rows,
         return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
     const int32_t* cells = nullptr;
     int64_t n = 0;
-    MGP_TRY(var_population(st, s, n_rows, job, who, &cells, &n));
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
     for (int64_t v = 0; v < n_var; ++v)
         if (pos[v] < 0 || pos[v] >= rows.L || base[v] < 0 || base[v] > 3)
             return set_err(MGP_E_INVALID, std::string(who) + ": variant position or base out of range");
@@ -5283,6 +5291,235 @@ int mgp_allele_freq_rows(int device, const uint32_t* counts, const uint32_t* dep
                        [&](VarState& st, hipStream_t s, const txtgz::Rows& rows) {
                            return var_allele_freq(st, s, rows, n_rows, job, n_var, pos, base, min_coverage, out);
                        });
+}
+
+// ---------------------------------------------------------------------------
+// mgp_cell_coverage_* / mgp_position_*: coverage QC from the count rows
+// (calculate_cell_coverage_stats ... calculate_transposition_stats, R/mgatk2_functions.R:138-280)
+// ---------------------------------------------------------------------------
+static int qc_sum_bounds(const txtgz::Rows& rows, const char* who) {
+    if (rows.L > qc::kMaxL)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 65536 positions (the exactness bound of the u64 sums)");
+    return MGP_OK;
+}
+
+static int qc_bad(QcState& st, hipStream_t s, const char* who) {
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad)
+        return set_err(MGP_E_INVALID, std::string(who) + ": a depth or count of the population is 2^24 or more (the "
+                                                         "exactness bound of the u64 sums)");
+    return MGP_OK;
+}
+
+static int qc_cell_coverage(QcState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows,
+                            const mgp_variant_job* job, mgp_cell_coverage* out) {
+    using namespace qc;
+    const char* who = "mgp_cell_coverage";
+    if (!out) return set_err(MGP_E_INVALID, std::string(who) + ": null output");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    MGP_TRY(qc_sum_bounds(rows, who));
+    if (n == 0) return MGP_OK;
+    if (!out->s_depth || !out->s_depth2 || !out->max_depth || !out->n_covered || !out->n_10x || !out->n_50x ||
+        !out->mid_lo || !out->mid_hi)
+        return set_err(MGP_E_INVALID, std::string(who) + ": null output array");
+    MGP_TRY(st.out64.ensure((size_t)n * CELL64_N * 8));
+    MGP_TRY(st.out32.ensure((size_t)n * CELL32_N * 4));
+    MGP_TRY(st.bad.ensure(4));
+    VarProf prof(s);
+    if (cell_stats(rows, cells, n, st.out64.as<unsigned long long>(), st.out32.as<uint32_t>(), st.bad.as<uint32_t>(),
+                   s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    MGP_TRY(qc_bad(st, s, who));
+    prof.report(who, "cells x positions", n, rows.L);
+    std::vector<uint64_t> h64((size_t)n * CELL64_N);
+    std::vector<uint32_t> h32((size_t)n * CELL32_N);
+    HIP_TRY(hipMemcpyAsync(h64.data(), st.out64.p, h64.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h32.data(), st.out32.p, h32.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    uint32_t* dst32[CELL32_N] = {out->max_depth, out->n_covered, out->n_10x, out->n_50x, out->mid_lo, out->mid_hi};
+    for (int64_t k = 0; k < n; ++k) {
+        out->s_depth[k] = h64[k * CELL64_N + CELL64_SD];
+        out->s_depth2[k] = h64[k * CELL64_N + CELL64_SD2];
+        for (int f = 0; f < CELL32_N; ++f) dst32[f][k] = h32[k * CELL32_N + f];
+    }
+    return MGP_OK;
+}
+
+static int qc_position_coverage(QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5& tn5,
+                                int32_t n_rows, const mgp_variant_job* job, mgp_position_coverage* out) {
+    using namespace qc;
+    const char* who = "mgp_position_coverage";
+    if (!out || !out->s_depth || !out->s_depth2 || !out->s_fwd || !out->s_rev || !out->s_tn5_fwd || !out->s_tn5_rev ||
+        !out->tally || !out->n_covered || !out->n_10x || !out->n_50x || !out->n_tn5 || !out->max_depth)
+        return set_err(MGP_E_INVALID, std::string(who) + ": null output array");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    MGP_TRY(qc_sum_bounds(rows, who));
+    const size_t L = (size_t)rows.L;
+    MGP_TRY(st.out64.ensure(L * POS64_N * 8));
+    MGP_TRY(st.out32.ensure(L * POS32_N * 4));
+    MGP_TRY(st.bad.ensure(4));
+    VarProf prof(s);
+    if (pos_stats(rows, tn5, cells, n, st.out64.as<unsigned long long>(), st.out32.as<uint32_t>(),
+                  st.bad.as<uint32_t>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    MGP_TRY(qc_bad(st, s, who));
+    prof.report(who, "cells x positions", n, rows.L);
+    uint64_t* dst64[POS64_TALLY] = {out->s_depth, out->s_depth2, out->s_fwd, out->s_rev, out->s_tn5_fwd, out->s_tn5_rev};
+    uint32_t* dst32[POS32_N] = {out->n_covered, out->n_10x, out->n_50x, out->n_tn5, out->max_depth};
+    const uint64_t* a64 = st.out64.as<uint64_t>();
+    const uint32_t* a32 = st.out32.as<uint32_t>();
+    for (int f = 0; f < POS64_TALLY; ++f) HIP_TRY(hipMemcpyAsync(dst64[f], a64 + f * L, L * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->tally, a64 + POS64_TALLY * L, L * 4 * 8, hipMemcpyDeviceToHost, s));
+    for (int f = 0; f < POS32_N; ++f) HIP_TRY(hipMemcpyAsync(dst32[f], a32 + f * L, L * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MGP_OK;
+}
+
+static int qc_depth_hist(QcState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const mgp_variant_job* job,
+                         int32_t shift, const uint32_t* prefix, uint32_t* hist) {
+    const char* who = "mgp_position_depth_hist";
+    if (!hist || (shift != 0 && shift != 8 && shift != 16 && shift != 24) || (shift != 24 && !prefix))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments (shift is 0, 8, 16 or 24)");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    const size_t L = (size_t)rows.L;
+    MGP_TRY(st.in32.ensure(L * 4));
+    MGP_TRY(st.hist.ensure(L * 256 * 4));
+    if (shift != 24) HIP_TRY(hipMemcpyAsync(st.in32.p, prefix, L * 4, hipMemcpyHostToDevice, s));
+    VarProf prof(s);
+    if (qc::pos_depth_hist(rows, cells, n, shift, st.in32.as<uint32_t>(), st.hist.as<uint32_t>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    HIP_TRY(hipMemcpyAsync(hist, st.hist.p, L * 256 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "cells x positions", n, rows.L);
+    return MGP_OK;
+}
+
+static int qc_depth_next(QcState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const mgp_variant_job* job,
+                         const uint32_t* v, uint32_t* n_le, uint32_t* next) {
+    const char* who = "mgp_position_depth_next";
+    if (!v || !n_le || !next) return set_err(MGP_E_INVALID, std::string(who) + ": null array");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    const size_t L = (size_t)rows.L;
+    MGP_TRY(st.in32.ensure(L * 4));
+    MGP_TRY(st.out32.ensure(L * 2 * 4));
+    HIP_TRY(hipMemcpyAsync(st.in32.p, v, L * 4, hipMemcpyHostToDevice, s));
+    uint32_t* o = st.out32.as<uint32_t>();
+    VarProf prof(s);
+    if (qc::pos_depth_next(rows, cells, n, st.in32.as<uint32_t>(), o, o + L, s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    HIP_TRY(hipMemcpyAsync(n_le, o, L * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(next, o + L, L * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "cells x positions", n, rows.L);
+    return MGP_OK;
+}
+
+static qc::Tn5 qc_ctx_tn5(mgp_ctx* ctx) { return qc::Tn5{ctx->tn5_16.as<uint32_t>(), ctx->tn5.as<uint32_t>()}; }
+
+int mgp_cell_coverage_run(mgp_ctx* ctx, const mgp_variant_job* job, mgp_cell_coverage* out) {
+    txtgz::Rows rows{};
+    MGP_TRY(var_ctx_rows(ctx, "mgp_cell_coverage_run", &rows));
+    return qc_cell_coverage(ctx->qc, ctx->s_comp, rows, ctx->g.nc, job, out);
+}
+
+int mgp_position_coverage_run(mgp_ctx* ctx, const mgp_variant_job* job, mgp_position_coverage* out) {
+    txtgz::Rows rows{};
+    MGP_TRY(var_ctx_rows(ctx, "mgp_position_coverage_run", &rows));
+    return qc_position_coverage(ctx->qc, ctx->s_comp, rows, qc_ctx_tn5(ctx), ctx->g.nc, job, out);
+}
+
+int mgp_position_depth_hist_run(mgp_ctx* ctx, const mgp_variant_job* job, int32_t shift, const uint32_t* prefix,
+                                uint32_t* hist) {
+    txtgz::Rows rows{};
+    MGP_TRY(var_ctx_rows(ctx, "mgp_position_depth_hist_run", &rows));
+    return qc_depth_hist(ctx->qc, ctx->s_comp, rows, ctx->g.nc, job, shift, prefix, hist);
+}
+
+int mgp_position_depth_next_run(mgp_ctx* ctx, const mgp_variant_job* job, const uint32_t* v, uint32_t* n_le,
+                                uint32_t* next) {
+    txtgz::Rows rows{};
+    MGP_TRY(var_ctx_rows(ctx, "mgp_position_depth_next_run", &rows));
+    return qc_depth_next(ctx->qc, ctx->s_comp, rows, ctx->g.nc, job, v, n_le, next);
+}
+
+// the *_rows forms: the caller's u32 rows uploaded (tn5 may be null where `fn` reads none)
+static int qc_on_rows(int device, const uint32_t* counts, const uint32_t* tn5, const uint32_t* depth, int32_t n_rows,
+                      int32_t mito_len, const char* who,
+                      const std::function<int(QcState&, hipStream_t, const txtgz::Rows&, const qc::Tn5&)>& fn) {
+    if (n_rows < 0 || mito_len <= 0 || (n_rows > 0 && !depth))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    int rc = MGP_OK;
+    {
+        QcState st;
+        const size_t npos = (size_t)n_rows * (size_t)mito_len;
+        rc = st.rows_d.ensure(npos * 4 + 64);
+        if (rc == MGP_OK && counts) rc = st.rows_c.ensure(npos * 32 + 64);
+        if (rc == MGP_OK && tn5) rc = st.rows_t.ensure(npos * 8 + 64);
+        if (rc == MGP_OK && npos) {
+            if (hipMemcpy(st.rows_d.p, depth, npos * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                (counts && hipMemcpy(st.rows_c.p, counts, npos * 32, hipMemcpyHostToDevice) != hipSuccess) ||
+                (tn5 && hipMemcpy(st.rows_t.p, tn5, npos * 8, hipMemcpyHostToDevice) != hipSuccess))
+                rc = set_err(MGP_E_HIP, std::string(who) + ": upload failed");
+        }
+        txtgz::Rows rows{nullptr, nullptr, nullptr, st.rows_c.as<uint32_t>(), st.rows_d.as<uint32_t>(), mito_len,
+                         mito_len, 1};
+        const qc::Tn5 t{nullptr, st.rows_t.as<uint32_t>()};
+        if (rc == MGP_OK) rc = fn(st, s, rows, t);
+        (void)hipStreamSynchronize(s);
+    }
+    (void)hipStreamDestroy(s);
+    return rc;
+}
+
+int mgp_cell_coverage_rows(int device, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                           const mgp_variant_job* job, mgp_cell_coverage* out) {
+    return qc_on_rows(device, nullptr, nullptr, depth, n_rows, mito_len, "mgp_cell_coverage_rows",
+                      [&](QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+                          return qc_cell_coverage(st, s, rows, n_rows, job, out);
+                      });
+}
+
+int mgp_position_coverage_rows(int device, const uint32_t* counts, const uint32_t* tn5, const uint32_t* depth,
+                               int32_t n_rows, int32_t mito_len, const mgp_variant_job* job,
+                               mgp_position_coverage* out) {
+    if (n_rows > 0 && (!counts || !tn5)) return set_err(MGP_E_INVALID, "mgp_position_coverage_rows: bad arguments");
+    return qc_on_rows(device, counts, tn5, depth, n_rows, mito_len, "mgp_position_coverage_rows",
+                      [&](QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5& t) {
+                          return qc_position_coverage(st, s, rows, t, n_rows, job, out);
+                      });
+}
+
+int mgp_position_depth_hist_rows(int device, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                                 const mgp_variant_job* job, int32_t shift, const uint32_t* prefix, uint32_t* hist) {
+    return qc_on_rows(device, nullptr, nullptr, depth, n_rows, mito_len, "mgp_position_depth_hist_rows",
+                      [&](QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+                          return qc_depth_hist(st, s, rows, n_rows, job, shift, prefix, hist);
+                      });
+}
+
+int mgp_position_depth_next_rows(int device, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                                 const mgp_variant_job* job, const uint32_t* v, uint32_t* n_le, uint32_t* next) {
+    return qc_on_rows(device, nullptr, nullptr, depth, n_rows, mito_len, "mgp_position_depth_next_rows",
+                      [&](QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+                          return qc_depth_next(st, s, rows, n_rows, job, v, n_le, next);
+                      });
 }
 
 }  // extern "C"

@@ -5,101 +5,26 @@
 // consecutive positions of a cell (1 KB of its uint4 rows), and a loop over a slab of the
 // population's cells. grid.x = ceil(L / 256) position blocks, grid.y = cell slabs: chrM's
 // 16,569 positions alone are 65 workgroups, the slabs bring the grid to ~1000.
-// Every workgroup stages, per chunk of kChunk cells, their row indices and the wide flags
-// of the windows its positions touch in LDS (the rows are txtgz::Rows: 16-bit rows, with
-// the exact u32 rows where a (cell, window) was drained).
+// The loop over the cells is sweep() of mgp_sweep.h, which mgp_qc.hip shares.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 
+#include "mgp_sweep.h"
 #include "mgp_variants.h"
 
 namespace mgp {
 namespace variants {
 
+using sweep_detail::Cnt;
+using sweep_detail::kBlock;
+using sweep_detail::load_row;
+using sweep_detail::sweep;
+using sweep_detail::wide_at;
 using txtgz::Rows;
 
-constexpr int kBlock = 256;  // positions per workgroup
-constexpr int kChunk = 128;  // cells whose indices and wide flags are staged at once
-constexpr int kWB = 4;       // windows a workgroup's positions may touch with staged flags
-constexpr int kUnroll = 4;   // rows in flight per thread
 constexpr int kTargetGroups = 1024;  // ~4 workgroups per CU
-
-struct Cnt {
-    uint32_t f[4], r[4], cov;
-};
-
-__device__ __forceinline__ bool wide_at(const Rows& r, int c, int win) {
-    return r.c16 == nullptr || (r.wide && r.wide[(size_t)c * r.nwin + win]);
-}
-
-// the counts of position p of row c (c < 0: zeros); u16: its window has exact 16-bit rows
-__device__ __forceinline__ void load_row(const Rows& r, int c, int p, bool u16, Cnt& x) {
-    if (c < 0) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) x.f[b] = x.r[b] = 0;
-        x.cov = 0;
-        return;
-    }
-    const size_t P = (size_t)c * r.L + p;
-    if (u16) {
-        const uint4 q = r.c16[P];
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            x.f[b] = w[b] & 0xFFFFu;
-            x.r[b] = w[b] >> 16;
-        }
-        x.cov = r.d16[P];
-    } else {
-        const uint4* q = reinterpret_cast<const uint4*>(r.c32 + P * 8);
-        const uint4 a = q[0], b2 = q[1];
-        x.f[0] = a.x, x.r[0] = a.y, x.f[1] = a.z, x.r[1] = a.w;
-        x.f[2] = b2.x, x.r[2] = b2.y, x.f[3] = b2.z, x.r[3] = b2.w;
-        x.cov = r.d32[P];
-    }
-}
-
-// Cells [k0, k1) of the population at this thread's position: acc.cell(x) for each, in
-// list order (kUnroll rows loaded ahead of their use). All threads of the workgroup call it.
-template <class Acc>
-__device__ __forceinline__ void sweep(const Rows& R, const int32_t* __restrict__ cells, int64_t k0, int64_t k1,
-                                      Acc& acc) {
-    __shared__ int32_t cs[kChunk + kUnroll];
-    __shared__ uint8_t wf[kChunk * kWB];
-    const int p0 = blockIdx.x * kBlock, p = p0 + (int)threadIdx.x;
-    const bool active = p < R.L;
-    const int w0 = p0 / R.W, w1 = min(R.L - 1, p0 + kBlock - 1) / R.W, nwb = w1 - w0 + 1;
-    const bool staged = nwb <= kWB;
-    const int myw = active ? p / R.W - w0 : 0;
-    for (int64_t kc = k0; kc < k1; kc += kChunk) {
-        const int m = (int)min((int64_t)kChunk, k1 - kc);
-        __syncthreads();  // (the previous chunk's readers are done)
-        for (int q = threadIdx.x; q < m + kUnroll; q += kBlock) cs[q] = q < m ? (cells ? cells[kc + q] : (int32_t)(kc + q)) : -1;
-        __syncthreads();
-        if (staged) {
-            for (int q = threadIdx.x; q < m * nwb; q += kBlock) {
-                const int i = q / nwb, w = q - i * nwb, c = cs[i];
-                wf[i * kWB + w] = (c >= 0 && wide_at(R, c, w0 + w)) ? 1 : 0;
-            }
-            __syncthreads();
-        }
-        if (!active) continue;
-        for (int i = 0; i < m; i += kUnroll) {
-            Cnt x[kUnroll];
-#pragma unroll
-            for (int j = 0; j < kUnroll; ++j) {
-                const int c = cs[i + j];  // (-1 past the chunk's end)
-                const bool u16 = c >= 0 && (staged ? !wf[min(i + j, kChunk - 1) * kWB + myw] : !wide_at(R, c, w0 + myw));
-                load_row(R, c, p, u16, x[j]);
-            }
-#pragma unroll
-            for (int j = 0; j < kUnroll; ++j)
-                if (i + j < m) acc.cell(x[j]);
-        }
-    }
-}
 
 struct MomentAcc {
     uint32_t thr;

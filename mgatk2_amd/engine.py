@@ -42,6 +42,9 @@ ABI_SYMBOLS = (
     "mgp_push_batch16", "mgp_txt_gz_run", "mgp_txt_gz_fetch", "mgp_txt_gz_rows", "mgp_set_rows_target",
     "mgp_h5_tiles_run", "mgp_h5_tiles_fetch", "mgp_variant_moments_run", "mgp_variant_dev2_run",
     "mgp_allele_freq_run", "mgp_variant_moments_rows", "mgp_variant_dev2_rows", "mgp_allele_freq_rows",
+    "mgp_cell_coverage_run", "mgp_position_coverage_run", "mgp_position_depth_hist_run",
+    "mgp_position_depth_next_run", "mgp_cell_coverage_rows", "mgp_position_coverage_rows",
+    "mgp_position_depth_hist_rows", "mgp_position_depth_next_rows",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -190,6 +193,25 @@ class mgp_variant_moments(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in MOMENT_FIELDS]
 
 
+# the arrays of mgp_cell_coverage ([n_cells]) and mgp_position_coverage ([L]; tally [L, 4]),
+# in their order, with their dtypes
+CELL_COVERAGE_FIELDS = (("s_depth", np.uint64), ("s_depth2", np.uint64), ("max_depth", np.uint32),
+                        ("n_covered", np.uint32), ("n_10x", np.uint32), ("n_50x", np.uint32), ("mid_lo", np.uint32),
+                        ("mid_hi", np.uint32))
+POSITION_COVERAGE_FIELDS = (("s_depth", np.uint64), ("s_depth2", np.uint64), ("s_fwd", np.uint64), ("s_rev", np.uint64),
+                            ("s_tn5_fwd", np.uint64), ("s_tn5_rev", np.uint64), ("tally", np.uint64),
+                            ("n_covered", np.uint32), ("n_10x", np.uint32), ("n_50x", np.uint32), ("n_tn5", np.uint32),
+                            ("max_depth", np.uint32))
+
+
+class mgp_cell_coverage(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _ in CELL_COVERAGE_FIELDS]
+
+
+class mgp_position_coverage(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _ in POSITION_COVERAGE_FIELDS]
+
+
 H5_PLANES = ("A_fwd", "A_rev", "C_fwd", "C_rev", "G_fwd", "G_rev", "T_fwd", "T_rev", "tn5_cuts_fwd", "tn5_cuts_rev",
              "coverage")  # the planes of mgp_h5_tiles, in its order
 
@@ -276,6 +298,18 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_allele_freq_rows": (
             [C.c_int, vp, vp, i32, i32, C.POINTER(mgp_variant_job), i64, vp, vp, i32, vp], C.c_int
         ),
+        "mgp_cell_coverage_run": ([vp, C.POINTER(mgp_variant_job), C.POINTER(mgp_cell_coverage)], C.c_int),
+        "mgp_position_coverage_run": ([vp, C.POINTER(mgp_variant_job), C.POINTER(mgp_position_coverage)], C.c_int),
+        "mgp_position_depth_hist_run": ([vp, C.POINTER(mgp_variant_job), i32, vp, vp], C.c_int),
+        "mgp_position_depth_next_run": ([vp, C.POINTER(mgp_variant_job), vp, vp, vp], C.c_int),
+        "mgp_cell_coverage_rows": (
+            [C.c_int, vp, i32, i32, C.POINTER(mgp_variant_job), C.POINTER(mgp_cell_coverage)], C.c_int
+        ),
+        "mgp_position_coverage_rows": (
+            [C.c_int, vp, vp, vp, i32, i32, C.POINTER(mgp_variant_job), C.POINTER(mgp_position_coverage)], C.c_int
+        ),
+        "mgp_position_depth_hist_rows": ([C.c_int, vp, i32, i32, C.POINTER(mgp_variant_job), i32, vp, vp], C.c_int),
+        "mgp_position_depth_next_rows": ([C.c_int, vp, i32, i32, C.POINTER(mgp_variant_job), vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -600,6 +634,84 @@ def allele_freq_rows(counts: np.ndarray, depth: np.ndarray, variants, cells=None
     return _rows_calls(counts, depth, device)[2](variants, cells, min_coverage)
 
 
+def _coverage_calls(call, n_rows: int, L: int):
+    """The four coverage QC passes over one row source: call(name, *args) runs mgp_<name>_run
+    on a context or mgp_<name>_rows on caller rows. Each returns a dict of numpy arrays."""
+
+    def cell_coverage(cells=None) -> dict:
+        job, keep = _variant_job(cells)
+        n = n_rows if keep is None else keep.shape[0]
+        out = {k: np.zeros(n, dt) for k, dt in CELL_COVERAGE_FIELDS}
+        call("mgp_cell_coverage", C.byref(job),
+             C.byref(mgp_cell_coverage(*[_ptr(out[k]) for k, _ in CELL_COVERAGE_FIELDS])))
+        return out
+
+    def position_coverage(cells=None) -> dict:
+        job, keep = _variant_job(cells)
+        out = {k: np.zeros((L, 4) if k == "tally" else L, dt) for k, dt in POSITION_COVERAGE_FIELDS}
+        call("mgp_position_coverage", C.byref(job),
+             C.byref(mgp_position_coverage(*[_ptr(out[k]) for k, _ in POSITION_COVERAGE_FIELDS])))
+        return out
+
+    def position_depth_hist(shift: int, prefix=None, cells=None) -> dict:
+        job, keep = _variant_job(cells)
+        pre = np.zeros(L, np.uint32) if prefix is None else np.ascontiguousarray(prefix, np.uint32)
+        if pre.shape != (L,):
+            raise InvalidInputError("prefix must be [mito_len]")
+        hist = np.zeros((L, 256), np.uint32)
+        call("mgp_position_depth_hist", C.byref(job), int(shift), _ptr(pre), _ptr(hist))
+        return {"hist": hist}
+
+    def position_depth_next(v, cells=None) -> dict:
+        job, keep = _variant_job(cells)
+        at = np.ascontiguousarray(v, np.uint32)
+        if at.shape != (L,):
+            raise InvalidInputError("v must be [mito_len]")
+        n_le, nxt = np.zeros(L, np.uint32), np.zeros(L, np.uint32)
+        call("mgp_position_depth_next", C.byref(job), _ptr(at), _ptr(n_le), _ptr(nxt))
+        return {"n_le": n_le, "next": nxt}
+
+    return cell_coverage, position_coverage, position_depth_hist, position_depth_next
+
+
+def _coverage_rows_calls(counts, tn5, depth: np.ndarray, device: int):
+    lib = load_library()
+    depth = np.ascontiguousarray(depth, np.uint32)
+    n_rows, L = depth.shape
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, np.uint32)
+        tn5 = np.ascontiguousarray(tn5, np.uint32)
+        if counts.shape != (n_rows, L, 8) or tn5.shape != (n_rows, L, 2):
+            raise InvalidInputError("counts must be [n, L, 8] and tn5 [n, L, 2]")
+
+    def call(name, *args):
+        rows = (_ptr(counts), _ptr(tn5), _ptr(depth)) if name == "mgp_position_coverage" else (_ptr(depth),)
+        _ck(getattr(lib, name + "_rows")(int(device), *rows, int(n_rows), int(L), *args), name + "_rows")
+
+    return _coverage_calls(call, n_rows, L)
+
+
+def cell_coverage_rows(depth: np.ndarray, cells=None, device: int = 0) -> dict:
+    """mgp_cell_coverage_rows: Engine.cell_coverage on caller-supplied u32 depths [n, L]."""
+    return _coverage_rows_calls(None, None, depth, device)[0](cells)
+
+
+def position_coverage_rows(counts: np.ndarray, tn5: np.ndarray, depth: np.ndarray, cells=None, device: int = 0) -> dict:
+    """mgp_position_coverage_rows: Engine.position_coverage on caller-supplied u32 rows (counts
+    [n, L, 8], tn5 [n, L, 2], depth [n, L])."""
+    return _coverage_rows_calls(counts, tn5, depth, device)[1](cells)
+
+
+def position_depth_hist_rows(depth: np.ndarray, shift: int, prefix=None, cells=None, device: int = 0) -> dict:
+    """mgp_position_depth_hist_rows: Engine.position_depth_hist on caller-supplied u32 depths."""
+    return _coverage_rows_calls(None, None, depth, device)[2](shift, prefix, cells)
+
+
+def position_depth_next_rows(depth: np.ndarray, v, cells=None, device: int = 0) -> dict:
+    """mgp_position_depth_next_rows: Engine.position_depth_next on caller-supplied u32 depths."""
+    return _coverage_rows_calls(None, None, depth, device)[3](v, cells)
+
+
 class Engine:
     """One device context (one GPU). Not thread-safe."""
 
@@ -806,6 +918,35 @@ class Engine:
             _ck(getattr(self.lib, name + "_run")(self._h, *args), name + "_run")
 
         return _variant_calls(call, self.cfg.n_cells, self.cfg.mito_len)
+
+    def _coverage_calls(self):
+        def call(name, *args):
+            _ck(getattr(self.lib, name + "_run")(self._h, *args), name + "_run")
+
+        return _coverage_calls(call, self.cfg.n_cells, self.cfg.mito_len)
+
+    def cell_coverage(self, cells=None) -> dict:
+        """mgp_cell_coverage_run (after run()): per cell of the population `cells` (as for
+        variant_moments), over all mito_len positions: CELL_COVERAGE_FIELDS arrays [n]: the
+        depth's exact sum and sum of squares, max, the positions with depth > 0, >= 10,
+        >= 50, and the two middle order statistics. Depths below 2^24, mito_len <= 2^16."""
+        return self._coverage_calls()[0](cells)
+
+    def position_coverage(self, cells=None) -> dict:
+        """mgp_position_coverage_run: per position over the population, POSITION_COVERAGE_FIELDS
+        arrays [L] (tally [L, 4]): the depth, strand and Tn5 sums, the cell counts and the max.
+        At most VARIANT_MAX_CELLS cells per call, every depth and count below 2^24."""
+        return self._coverage_calls()[1](cells)
+
+    def position_depth_hist(self, shift: int, prefix=None, cells=None) -> dict:
+        """mgp_position_depth_hist_run: {"hist": uint32 [L, 256]}, one round of the radix
+        select over cells (analysis/coverage.py: position_medians drives it)."""
+        return self._coverage_calls()[2](shift, prefix, cells)
+
+    def position_depth_next(self, v, cells=None) -> dict:
+        """mgp_position_depth_next_run: {"n_le": cells with depth <= v[p], "next": the smallest
+        depth > v[p] (0xFFFFFFFF: none)}, uint32 [L] each."""
+        return self._coverage_calls()[3](v, cells)
 
     def variant_moments(self, cells=None, low_coverage_threshold: int = 0) -> dict:
         """mgp_variant_moments_run (pass 1 of the variant statistics, after run()): the

@@ -95,6 +95,10 @@ class MtDNAPipeline:
         variant_stabilize: bool = False,
         variant_low_coverage: int = 10,
         variant_min_coverage: int = 1,
+        coverage_stats: bool = False,
+        cell_min_mean_coverage: float = 0.0,
+        cell_min_coverage_breadth: float = 0.0,
+        recompute_reference: bool = False,
     ):
         self.bam_path = Path(bam_path)
         # streamed ingest (default; MGP_STREAM=0 decodes the whole chrM set first)
@@ -116,6 +120,14 @@ class MtDNAPipeline:
         self.variant_options = dict(min_cells=variant_min_cells, min_strand_cor=variant_min_strand_cor,
                                     min_vmr=variant_min_vmr, stabilize_variance=bool(variant_stabilize),
                                     low_coverage_threshold=variant_low_coverage, min_coverage=variant_min_coverage)
+        # coverage QC from the devices' rows (off unless asked for): coverage/ in the output; the
+        # cell filter and the recomputed reference also set the variants' population and reference
+        self.coverage_stats = bool(coverage_stats)
+        self.coverage_options = dict(min_mean_coverage=float(cell_min_mean_coverage),
+                                     min_coverage_breadth=float(cell_min_coverage_breadth),
+                                     recompute_reference=bool(recompute_reference))
+        self.coverage_on = (self.coverage_stats or bool(recompute_reference) or cell_min_mean_coverage > 0
+                            or cell_min_coverage_breadth > 0)
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -165,6 +177,8 @@ class MtDNAPipeline:
             processor.enable_device_h5(self.barcode_list)
         if self.call_variants:
             processor.enable_variants(**self.variant_options)
+        if self.coverage_on:
+            processor.enable_coverage(**self.coverage_options)
         if self.stream:
             # one pass: batches decoded on a producer thread, each pushed to the device as
             # it is ready, the windows piled as their reads arrive (readers.py:84-93)
@@ -218,11 +232,20 @@ class MtDNAPipeline:
         meta = QCCalculator(self.config).collect_run_metadata(
             str(self.bam_path), str(self.output_dir), n_cells_input, len(cell_results))
         write_run_summary(meta, qc_dir / "summary.txt")
+        cov = getattr(res, "coverage", None) if self.coverage_on else None
+        if cov is not None and (self.coverage_stats or cov.ref_alleles is not None):
+            from .analysis.coverage import write_coverage_outputs
+            from .file_io.writers import ref_alleles
+
+            write_coverage_outputs(cov, self.barcode_list, self.output_dir, ref_alleles(res.ref_tally),
+                                   tables=self.coverage_stats)
+            logger.info("%d of %d cells kept by the coverage filter", int(cov.kept.sum()), int(cov.kept.size))
         if self.call_variants and getattr(res, "variants", None) is not None:
             from .analysis.variants import write_variant_outputs
 
-            write_variant_outputs(res.variants, res.allele_freq, self.barcode_list, self.output_dir,
-                                  self.output_format)
+            kept = getattr(res, "variant_cells", None)  # (the coverage filter's kept cells: the matrix's columns)
+            names = self.barcode_list if kept is None else [self.barcode_list[int(i)] for i in kept]
+            write_variant_outputs(res.variants, res.allele_freq, names, self.output_dir, self.output_format)
             logger.info("%d variants called", len(res.variants))
         t3 = time.time()
         gc.collect()
@@ -291,11 +314,19 @@ def run_pipeline(
     variant_stabilize: bool = False,
     variant_low_coverage: int = 10,
     variant_min_coverage: int = 1,
+    coverage_stats: bool = False,
+    cell_min_mean_coverage: float = 0.0,
+    cell_min_coverage_breadth: float = 0.0,
+    recompute_reference: bool = False,
 ) -> dict[str, Any]:
     """pipeline.py:183-269. ``min_distance_from_end`` is accepted and, as in the
     reference, not passed on (the engine uses 5). ``call_variants``
     (not in the reference's pipeline: its R step on counts.h5) writes variants/ with
-    mgatk's customary thresholds as defaults."""
+    mgatk's customary thresholds as defaults. ``coverage_stats`` writes coverage/ (the front
+    half of that R workflow: cell, position, strand and transposition tables);
+    ``cell_min_mean_coverage`` / ``cell_min_coverage_breadth`` filter the cells those position
+    tables and the variants are made of, ``recompute_reference`` gives the variants the kept
+    cells' own reference alleles (and writes coverage/reference_alleles.tsv)."""
     barcode_metadata = None
     if barcode_file is None:
         from .file_io.barcode_extraction import extract_barcodes_from_bam
@@ -333,6 +364,8 @@ def run_pipeline(
         device=device, devices=devices, call_variants=call_variants, variant_min_cells=variant_min_cells,
         variant_min_strand_cor=variant_min_strand_cor, variant_min_vmr=variant_min_vmr,
         variant_stabilize=variant_stabilize, variant_low_coverage=variant_low_coverage,
-        variant_min_coverage=variant_min_coverage,
+        variant_min_coverage=variant_min_coverage, coverage_stats=coverage_stats,
+        cell_min_mean_coverage=cell_min_mean_coverage, cell_min_coverage_breadth=cell_min_coverage_breadth,
+        recompute_reference=recompute_reference,
     )
     return pipeline.run()

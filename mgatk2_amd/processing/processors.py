@@ -114,6 +114,8 @@ class CellProcessor:
         self.txt_out = None
         self.h5_out = None
         self.variants_opt: dict | None = None
+        self.coverage_opt: dict | None = None
+        self._t_cov = self._t_var = 0.0
 
     # txt output on the device ----------------------------------------------
     def enable_device_txt(self, prefix, names: list[str]):
@@ -153,11 +155,63 @@ class CellProcessor:
         from ..file_io.writers import ref_alleles
 
         t0 = time.perf_counter()
-        n_cells = int(res.passed.shape[0])
-        pop = np.where(res.passed.astype(bool), np.arange(n_cells, dtype=np.int64), -1)
-        vr = run_variants(parts, ref_alleles(res.ref_tally), cells=pop, **self.variants_opt)
+        pop, ref = self._population(res), ref_alleles(res.ref_tally)
+        res.variant_cells = None
+        cov = getattr(res, "coverage", None)
+        if self.coverage_opt is not None and cov is not None:
+            # the vignette's order: the variants of the kept cells, with their own reference
+            res.variant_cells = np.flatnonzero(cov.kept)
+            pop = cov.kept_cells
+            if cov.ref_alleles is not None:
+                ref = cov.ref_alleles
+        vr = run_variants(parts, ref, cells=pop, **self.variants_opt)
         res.variants, res.allele_freq, res.variant_seconds = vr.table, vr.allele_freq, vr.seconds
         return time.perf_counter() - t0
+
+    @staticmethod
+    def _population(res: EngineResult) -> np.ndarray:
+        """The run's default population: every cell, -1 (an all-zero row) for those that did
+        not pass, the zero columns of counts.h5."""
+        n_cells = int(res.passed.shape[0])
+        return np.where(res.passed.astype(bool), np.arange(n_cells, dtype=np.int64), -1)
+
+    def enable_coverage(self, min_mean_coverage: float = 0.0, min_coverage_breadth: float = 0.0,
+                        recompute_reference: bool = False):
+        """Coverage QC from the devices' rows before their contexts close (mgp_cell_coverage_*,
+        mgp_position_*; analysis/coverage.py): the run's result then carries `coverage`, a
+        CoverageResult with the cell table over every cell of the run (cells that did not
+        pass count as all-zero rows), the kept mask of filter_cells_by_coverage (both
+        thresholds inclusive; at 0 every cell is kept), the position, strand and
+        transposition tables of the kept cells and, with recompute_reference, their
+        reference alleles. With enable_variants too, the variants are called over the kept
+        cells (allele_freq has one column per kept cell, `variant_cells` their indices), with
+        the recomputed reference when there is one."""
+        self.coverage_opt = dict(min_mean_coverage=float(min_mean_coverage),
+                                 min_coverage_breadth=float(min_coverage_breadth),
+                                 recompute_reference=bool(recompute_reference))
+
+    def _call_coverage(self, res: EngineResult, parts: list) -> float:
+        from ..analysis.coverage import run_coverage
+
+        t0 = time.perf_counter()
+        res.coverage = run_coverage(parts, cells=self._population(res), **self.coverage_opt)
+        return time.perf_counter() - t0
+
+    def _call_analyses(self, res: EngineResult, parts: list) -> float:
+        """The coverage pass, then the variants (which use its kept cells), over parts =
+        [(engine, lo, hi)] while their contexts are open. Returns the seconds spent."""
+        self._t_cov = self._t_var = 0.0
+        if parts and self.coverage_opt is not None:
+            self._t_cov = self._call_coverage(res, parts)
+        if parts and self.variants_opt is not None:
+            self._t_var = self._call_variants(res, parts)
+        return self._t_cov + self._t_var
+
+    def _analysis_timing(self):
+        if self.coverage_opt is not None:
+            self.last_timing["coverage"] = self._t_cov
+        if self.variants_opt is not None:
+            self.last_timing["variants"] = self._t_var
 
     def _h5_device_on(self) -> bool:
         return self.h5_out is not None and os.environ.get("MGP_H5_DEVICE", "1") != "0"
@@ -330,14 +384,13 @@ class CellProcessor:
             self.last_stats = eng.kernel_times()
             t_txt = self._write_txt(res, [(eng, 0, n_cells)]) if self._txt_device_on() else 0.0
             t_h5 = self._write_h5(res, [(eng, 0, n_cells)]) if self._h5_device_on() else 0.0
-            t_var = self._call_variants(res, [(eng, 0, n_cells)]) if self.variants_opt is not None else 0.0
+            t_var = self._call_analyses(res, [(eng, 0, n_cells)])
         t4 = time.perf_counter()
         # where the engine leg goes (pipeline timings): context + allocation, H2D of
         # the batches + the run, D2H of the results, teardown
         self.last_timing = {"engine_open": t1 - t0, "engine_h2d_run": t2 - t1, "engine_d2h": t3 - t2,
                             "engine_close": t4 - t3 - t_txt - t_h5 - t_var, "txt_device": t_txt, "h5_device": t_h5}
-        if self.variants_opt is not None:
-            self.last_timing["variants"] = t_var
+        self._analysis_timing()
         self.last_result = res
         return res
 
@@ -505,7 +558,7 @@ class CellProcessor:
                 _, last_streamed = eng.stream_info()
                 t_txt = self._write_txt(res, [(eng, 0, n_cells)]) if self._txt_device_on() else 0.0
                 t_h5 = self._write_h5(res, [(eng, 0, n_cells)]) if self._h5_device_on() else 0.0
-                t_var = self._call_variants(res, [(eng, 0, n_cells)]) if self.variants_opt is not None else 0.0
+                t_var = self._call_analyses(res, [(eng, 0, n_cells)])
             finally:
                 free.put(None)
                 eng.close()
@@ -524,8 +577,7 @@ class CellProcessor:
                             "stream_batches": n_batches, "stream_batch_reads": times["cap_reads"],
                             "streamed_run": bool(last_streamed), "rows_target": rows is not None,
                             "h2d_bytes": int(h2d)}
-        if self.variants_opt is not None:
-            self.last_timing["variants"] = t_var
+        self._analysis_timing()
         self.last_result = res
         return res
 
@@ -756,8 +808,7 @@ class CellProcessor:
                 if parts and self._txt_device_on() else 0.0
             t_h5 = self._write_h5(res, [(engines[d], lo, hi) for d, lo, hi in parts]) \
                 if parts and self._h5_device_on() else 0.0
-            t_var = self._call_variants(res, [(engines[d], lo, hi) for d, lo, hi in parts]) \
-                if parts and self.variants_opt is not None else 0.0
+            t_var = self._call_analyses(res, [(engines[d], lo, hi) for d, lo, hi in parts])
         finally:
             free.put(None)
             for eng in engines.values():
@@ -774,8 +825,7 @@ class CellProcessor:
                             "stream_devices": len(parts), "rows_target": rows is not None, "route_s": t_route,
                             "h2d_bytes": int(sum(link_bytes.values())),
                             "cell_bounds": [lo for _, lo, _ in parts] + ([parts[-1][2]] if parts else [])}
-        if self.variants_opt is not None:
-            self.last_timing["variants"] = t_var
+        self._analysis_timing()
         self.last_result = res
         return res
 
@@ -792,7 +842,7 @@ class CellProcessor:
         b = partition_cells(reads_per_cell(soa, n_cells), len(self.devices))
         shards = [(int(lo), int(hi)) + shard_soa(soa, int(lo), int(hi)) for lo, hi in zip(b[:-1], b[1:])]
 
-        engines: list = [None] * len(self.devices)  # open until the variants are called from their rows
+        engines: list = [None] * len(self.devices)  # open until the coverage and variant passes have read their rows
 
         def one(i):
             lo, hi, sub, idx = shards[i]
@@ -804,16 +854,18 @@ class CellProcessor:
                 eng.run()
                 return eng.fetch_compact(), lo, hi, idx
             finally:
-                if self.variants_opt is None:
+                if self.variants_opt is None and self.coverage_opt is None:
                     eng.close()
 
         try:
             with ThreadPoolExecutor(len(self.devices)) as ex:
                 parts = list(ex.map(one, range(len(self.devices))))
             res = merge_results(parts, n_cells, soa.n)
-            if self.variants_opt is not None:
+            if self.variants_opt is not None or self.coverage_opt is not None:
                 live = [(engines[i], lo, hi) for i, (_, lo, hi, _) in enumerate(parts) if hi > lo]
-                self.last_timing = {"variants": self._call_variants(res, live) if live else 0.0}
+                self._call_analyses(res, live)
+                self.last_timing = {}
+                self._analysis_timing()
         finally:
             for eng in engines:
                 if eng is not None:
