@@ -93,7 +93,8 @@ def crafted():
 
 @pytest.mark.parametrize("pop", ["all", "subset", "holes", "one", "two", "empty"])
 def test_crafted_rows(engine_lib, crafted, pop):
-    """150 rows cross the 128-cell staging chunk and give several cell slabs; 333 positions are
+    """150 rows give five cell slabs of 30, each a single staging chunk (slabs of more than 128
+    cells, which stage twice: tests/test_gpu_sweep_slabs.py); 333 positions are
     one full and one ragged 256-position block and a ragged 64-position block. Columns: all
     zero, constant, differing middles, depths in each byte range up to 2^24 - 1, Tn5 cuts at a
     depth-0 position, ties across the middle."""
