@@ -1,0 +1,769 @@
+// mgp_jobs.hip — the host drivers of everything that reads a finished run's rows, and
+// their C-ABI entry points (include/mgpileup.h): the txt and HDF5 writers (kernels in
+// mgp_txtgz.hip), the variant statistics (mgp_variants.hip) and the coverage QC passes
+// (mgp_qc.hip). Each job has two forms: *_run on a context's last run, whose rows it gets
+// through run_rows (mgp_jobs.h: the context itself is opaque here), and the detached
+// *_rows form on u32 rows of the caller's (on_rows).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../include/mgpileup.h"
+#include "mgp_host.h"
+#include "mgp_jobs.h"
+#include "mgp_qc.h"
+#include "mgp_txtgz.h"
+#include "mgp_variants.h"
+
+using namespace mgp;
+
+// mgp_txt_gz: the device txt writer's buffers (mgp_txtgz.hip), kept for the next call
+struct TxtState {
+    DevBuf cells, names, name_off, sizes, nlines, offs, text, tok, lines, out, member_bytes, crc_shift, dst_off, packed;
+    DevBuf prof;  // MGP_TXT_PROF
+    DevBuf seg, crc;
+    bool shift_ready = false;
+    int64_t n = 0;
+    uint64_t total = 0;
+};
+
+// mgp_h5_tiles: the HDF5 chunk deflate's buffers (mgp_txtgz.hip), kept for the next call
+struct H5State {
+    DevBuf coc, raw, tok, out, out_off, chunk_bytes, dst_off, packed, sums, prof;
+    uint64_t total = 0;
+};
+
+// mgp_variant_* / mgp_allele_freq_*: the variant reductions' buffers (mgp_variants.hip)
+struct VarState {
+    DevBuf cells, acc, part, f64, mu, pos, base, bad, out;
+};
+
+// mgp_cell_coverage_* / mgp_position_*: the coverage QC passes' buffers (mgp_qc.hip)
+struct QcState {
+    DevBuf cells, out64, out32, bad, in32, hist;
+};
+
+struct RowJobs {
+    TxtState txt;
+    H5State h5;
+    VarState var;
+    QcState qc;
+};
+RowJobs* row_jobs_new() { return new RowJobs(); }
+void row_jobs_free(RowJobs* jobs) { delete jobs; }
+
+// The detached (*_rows) forms: the planes of the caller's u32 rows that the entry point
+// needs are uploaded and `job(state, stream, rows, tn5)` runs on them with a fresh State,
+// on a stream of the call's own; everything is freed once that stream is idle. A needed
+// plane that is null (with rows to read) is refused before any device call.
+enum { PL_COUNTS = 1, PL_TN5 = 2, PL_DEPTH = 4 };
+struct HostRows {
+    const uint32_t *counts, *tn5, *depth;  // [n_rows][mito_len] x 8, 2, 1 words; null where not needed
+    int32_t n_rows, mito_len;
+};
+template <class State, class Job>
+static int on_rows(int device, const char* who, int need, const HostRows& h, Job&& job) {
+    const uint32_t* src[3] = {h.counts, h.tn5, h.depth};
+    const size_t row_bytes[3] = {32, 8, 4};  // per position
+    const int32_t n_rows = h.n_rows, mito_len = h.mito_len;
+    bool ok = n_rows >= 0 && mito_len > 0;
+    for (int k = 0; k < 3; ++k) ok = ok && !((need >> k & 1) && n_rows > 0 && !src[k]);
+    if (!ok) return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    int rc = MGP_OK;
+    {
+        State st;
+        DevBuf buf[3];
+        const size_t npos = (size_t)n_rows * (size_t)mito_len;
+        for (int k = 0; k < 3 && rc == MGP_OK; ++k)
+            if (need >> k & 1) rc = buf[k].ensure(npos * row_bytes[k] + 64);
+        for (int k = 0; k < 3 && rc == MGP_OK && npos; ++k)
+            if ((need >> k & 1) &&
+                hipMemcpy(buf[k].p, src[k], npos * row_bytes[k], hipMemcpyHostToDevice) != hipSuccess)
+                rc = set_err(MGP_E_HIP, std::string(who) + ": upload failed");
+        const txtgz::Rows rows{nullptr, nullptr, nullptr, buf[0].as<uint32_t>(), buf[2].as<uint32_t>(), mito_len,
+                               mito_len, 1};
+        const qc::Tn5 t{nullptr, buf[1].as<uint32_t>()};
+        if (rc == MGP_OK) rc = job(st, s, rows, t);
+        (void)hipStreamSynchronize(s);
+    }
+    (void)hipStreamDestroy(s);
+    return rc;
+}
+
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// mgp_txt_gz: the txt count files formatted and deflated on the device
+// (IncrementalTextWriter.write_cell + finalize's gzip -9, writers.py:430-486)
+// ---------------------------------------------------------------------------
+static int txt_run(TxtState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const mgp_txt_gz* job) {
+    using namespace txtgz;
+    const int64_t n = job->n_cells;
+    if (n < 0 || (n > 0 && (!job->cells || !job->names || !job->name_off || !job->member_bytes)))
+        return set_err(MGP_E_INVALID, "mgp_txt_gz: bad arguments");
+    st.n = n;
+    st.total = 0;
+    if (n == 0) return MGP_OK;
+    if (n > (int64_t)1 << 26) return set_err(MGP_E_INVALID, "mgp_txt_gz: too many cells for one call");
+    for (int64_t k = 0; k < n; ++k) {
+        if (job->cells[k] < 0 || job->cells[k] >= n_rows) return set_err(MGP_E_INVALID, "mgp_txt_gz: cell out of range");
+        const int64_t bl = job->name_off[k + 1] - job->name_off[k];
+        if (bl < 0 || bl > 4096 || job->name_off[k] < 0)
+            return set_err(MGP_E_INVALID, "mgp_txt_gz: barcode names of 0..4096 bytes");
+    }
+    const int64_t nm = kFiles * n;
+    const size_t nbytes = (size_t)job->name_off[n];
+    MGP_TRY(st.cells.ensure((size_t)n * 4));
+    MGP_TRY(st.names.ensure(nbytes + 1));
+    MGP_TRY(st.name_off.ensure((size_t)(n + 1) * 8));
+    MGP_TRY(st.sizes.ensure((size_t)nm * 8));
+    MGP_TRY(st.nlines.ensure((size_t)nm * 8));
+    MGP_TRY(st.offs.ensure((size_t)3 * (nm + 1) * 8));
+    MGP_TRY(st.member_bytes.ensure((size_t)nm * 4));
+    MGP_TRY(st.dst_off.ensure((size_t)nm * 8));
+    if (!st.shift_ready) {
+        std::vector<uint32_t> M(txtgz::kShiftPow * 32);
+        crc_shift_matrices(M.data());
+        MGP_TRY(st.crc_shift.ensure(M.size() * 4));
+        HIP_TRY(hipMemcpy(st.crc_shift.p, M.data(), M.size() * 4, hipMemcpyHostToDevice));
+        st.shift_ready = true;
+    }
+    HIP_TRY(hipMemcpyAsync(st.cells.p, job->cells, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (nbytes) HIP_TRY(hipMemcpyAsync(st.names.p, job->names, nbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(st.name_off.p, job->name_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+    Job jb{rows, n, st.cells.as<int32_t>(), st.names.as<char>(), st.name_off.as<int64_t>()};
+    if (txt_sizes(jb, st.sizes.as<uint64_t>(), st.nlines.as<uint64_t>(), s) != 0)
+        return set_err(MGP_E_HIP, "mgp_txt_gz: size kernel launch failed");
+    std::vector<uint64_t> sz((size_t)nm), nl((size_t)nm), offs((size_t)3 * (nm + 1));
+    HIP_TRY(hipMemcpyAsync(sz.data(), st.sizes.p, (size_t)nm * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(nl.data(), st.nlines.p, (size_t)nm * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    uint64_t* to = offs.data();
+    uint64_t* lo = to + nm + 1;
+    uint64_t* oo = lo + nm + 1;
+    to[0] = lo[0] = oo[0] = 0;
+    for (int64_t m = 0; m < nm; ++m) {
+        to[m + 1] = to[m] + ((sz[(size_t)m] + 15) & ~uint64_t(15));  // (aligned: the parse loads 16 bytes)
+        lo[m + 1] = lo[m] + nl[(size_t)m];
+        oo[m + 1] = oo[m] + out_bound(sz[(size_t)m]);
+        if (job->text_bytes) job->text_bytes[m] = (int64_t)sz[(size_t)m];
+    }
+    MGP_TRY(st.text.ensure(to[nm] + 256));  // (slack: a parse block reads up to 31 positions past a text)
+    MGP_TRY(st.tok.ensure(4 * to[nm] + 1024));
+    MGP_TRY(st.lines.ensure(12 * lo[nm] + 64));
+    MGP_TRY(st.out.ensure(oo[nm] + 64));
+    HIP_TRY(hipMemcpyAsync(st.offs.p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, s));
+    Scratch sc{};
+    sc.text_off = st.offs.as<uint64_t>();
+    sc.text_n = st.sizes.as<uint64_t>();
+    sc.line_off = sc.text_off + nm + 1;
+    sc.out_off = sc.line_off + nm + 1;
+    sc.text = st.text.as<uint8_t>();
+    sc.tok = st.tok.as<uint32_t>();
+    sc.lines = st.lines.as<uint32_t>();
+    sc.out = st.out.as<uint32_t>();
+    sc.member_bytes = st.member_bytes.as<uint32_t>();
+    sc.crc_shift = st.crc_shift.as<uint32_t>();
+    MGP_TRY(st.seg.ensure((size_t)nm * 257 * 4));
+    MGP_TRY(st.crc.ensure((size_t)nm * 4));
+    sc.seg = st.seg.as<uint32_t>();
+    sc.crc = st.crc.as<uint32_t>();
+    sc.prof = nullptr;
+    const bool prof = std::getenv("MGP_TXT_PROF") != nullptr;
+    if (prof) {
+        MGP_TRY(st.prof.ensure((size_t)nm * 64));
+        HIP_TRY(hipMemsetAsync(st.prof.p, 0, (size_t)nm * 64, s));
+        sc.prof = st.prof.as<uint64_t>();
+    }
+    if (txt_deflate(jb, sc, s) != 0) return set_err(MGP_E_HIP, "mgp_txt_gz: deflate kernel launch failed");
+    if (prof) {  // per-phase means over the members that have text (us), to stderr
+        std::vector<uint64_t> pr((size_t)nm * 8);
+        HIP_TRY(hipMemcpyAsync(pr.data(), st.prof.p, pr.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        // stamps: 0 format start, 1 format end, 2 match end, 3 parse end, 4 code end; each
+        // kernel's span over all members (first start to last end) and the mean per member
+        double mean[3] = {0, 0, 0};
+        uint64_t lo[3] = {UINT64_MAX, UINT64_MAX, UINT64_MAX}, hi[3] = {0, 0, 0};
+        int64_t cnt = 0;
+        for (int64_t m = 0; m < nm; ++m) {
+            const uint64_t* q = pr.data() + m * 8;
+            if (!q[4]) continue;
+            ++cnt;
+            mean[0] += (double)(q[1] - q[0]) * 0.01;
+            lo[0] = std::min(lo[0], q[0]);
+            hi[0] = std::max(hi[0], q[1]);
+            hi[1] = std::max(hi[1], q[2]);
+            hi[2] = std::max(hi[2], q[4]);
+            mean[2] += (double)(q[4] - q[3]) * 0.01;
+        }
+        // format phases per member: 0 start, 5 sizes + scan, 6 text written, 7 own CRC, 1 end
+        double fp[4] = {0, 0, 0, 0};
+        for (int64_t m = 0; m < nm; ++m) {
+            const uint64_t* q = pr.data() + m * 8;
+            if (!q[4]) continue;
+            fp[0] += (double)(q[5] - q[0]) * 0.01;
+            fp[1] += (double)(q[6] - q[5]) * 0.01;
+            fp[2] += (double)(q[7] - q[6]) * 0.01;
+            fp[3] += (double)(q[1] - q[7]) * 0.01;
+        }
+        std::fprintf(stderr, "[mgp_txt_gz] %lld members: format %.1f ms (%.1f us per member: sizes %.1f, text %.1f, "
+                     "crc %.1f, combine %.1f), match %.1f ms, code %.1f ms (tail %.1f us per member)\n", (long long)cnt,
+                     (hi[0] - lo[0]) * 1e-5, mean[0] / cnt, fp[0] / cnt, fp[1] / cnt, fp[2] / cnt, fp[3] / cnt,
+                     (hi[1] - hi[0]) * 1e-5, (hi[2] - hi[1]) * 1e-5, mean[2] / cnt);
+    }
+    std::vector<uint32_t> mb((size_t)nm);
+    HIP_TRY(hipMemcpyAsync(mb.data(), st.member_bytes.p, (size_t)nm * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<uint64_t> dst((size_t)nm);
+    uint64_t tot = 0;
+    for (int64_t m = 0; m < nm; ++m) {
+        dst[(size_t)m] = tot;
+        tot += mb[(size_t)m];
+        job->member_bytes[m] = mb[(size_t)m];
+    }
+    MGP_TRY(st.packed.ensure(tot + 64));
+    HIP_TRY(hipMemcpyAsync(st.dst_off.p, dst.data(), (size_t)nm * 8, hipMemcpyHostToDevice, s));
+    if (txt_pack(sc, nm, st.dst_off.as<uint64_t>(), st.packed.as<uint8_t>(), s) != 0)
+        return set_err(MGP_E_HIP, "mgp_txt_gz: pack kernel launch failed");
+    HIP_TRY(hipStreamSynchronize(s));
+    st.total = tot;
+    return MGP_OK;
+}
+
+int mgp_txt_gz_run(mgp_ctx* ctx, mgp_txt_gz* job, int64_t* total_bytes) {
+    if (!ctx || !job) return set_err(MGP_E_INVALID, "null ctx/job");
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_txt_gz: no run to write", &r));
+    MGP_TRY(txt_run(r.jobs->txt, r.stream, r.rows, r.n_cells, job));
+    if (total_bytes) *total_bytes = (int64_t)r.jobs->txt.total;
+    return MGP_OK;
+}
+
+int mgp_txt_gz_fetch(mgp_ctx* ctx, uint8_t* dst, int64_t cap) {
+    int device = 0;
+    const RowJobs* jobs = ctx ? ctx_jobs(ctx, &device) : nullptr;
+    if (!ctx || (!dst && jobs->txt.total)) return set_err(MGP_E_INVALID, "null ctx/dst");
+    if (cap < (int64_t)jobs->txt.total) return set_err(MGP_E_INVALID, "mgp_txt_gz_fetch: destination too small");
+    HIP_TRY(hipSetDevice(device));
+    if (jobs->txt.total) HIP_TRY(hipMemcpy(dst, jobs->txt.packed.p, jobs->txt.total, hipMemcpyDeviceToHost));
+    return MGP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// mgp_h5_tiles: the HDF5 count datasets' chunks deflated on the device
+// (IncrementalHDF5Writer, writers.py:60-131: 11 u16 planes, gzip-4 chunks of 1000 x 100)
+// ---------------------------------------------------------------------------
+int mgp_h5_tiles_run(mgp_ctx* ctx, mgp_h5_tiles* job, int64_t* total_bytes) {
+    using namespace txtgz;
+    if (!ctx || !job) return set_err(MGP_E_INVALID, "null ctx/job");
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_h5_tiles: no run to write", &r));
+    const int L = r.rows.L;
+    H5State& st = r.jobs->h5;
+    st.total = 0;
+    const int64_t nco = job->n_cols;
+    const int crow = job->chunk_rows, ccol = job->chunk_cols;
+    if (nco < 0 || crow <= 0 || ccol <= 0 || (int64_t)crow * ccol > (1 << 22) || !job->chunk_bytes ||
+        (nco > 0 && !job->cell_of_col))
+        return set_err(MGP_E_INVALID, "mgp_h5_tiles: bad arguments");
+    const int64_t ncc_all = (nco + ccol - 1) / ccol;
+    const int lo = job->col_chunk_lo, hi = job->col_chunk_hi;
+    if (lo < 0 || hi < lo || hi > ncc_all) return set_err(MGP_E_INVALID, "mgp_h5_tiles: column chunks out of range");
+    const int nrc = (L + crow - 1) / crow, ncc = hi - lo;
+    const int64_t nch = (int64_t)kPlanes * nrc * ncc;
+    if (nch == 0) {
+        if (total_bytes) *total_bytes = 0;
+        return MGP_OK;
+    }
+    if (nch > (int64_t)1 << 20) return set_err(MGP_E_INVALID, "mgp_h5_tiles: too many chunks for one call");
+    for (int64_t j = 0; j < nco; ++j)
+        if (job->cell_of_col[j] < -1 || job->cell_of_col[j] >= r.n_cells)
+            return set_err(MGP_E_INVALID, "mgp_h5_tiles: cell of a column out of range");
+    hipStream_t s = r.stream;
+    const uint64_t chunk_raw = (uint64_t)crow * ccol * 2, stride = out_bound(chunk_raw);
+    const uint64_t raw_stride = (chunk_raw + 15) & ~uint64_t(15);
+    MGP_TRY(st.coc.ensure((size_t)std::max<int64_t>(nco, 1) * 4));
+    MGP_TRY(st.raw.ensure((size_t)(nch * raw_stride) + 64));
+    MGP_TRY(st.tok.ensure((size_t)(nch * h5_tok_words(chunk_raw)) * 4 + 64));
+    MGP_TRY(st.out.ensure((size_t)(nch * stride) + 64));
+    MGP_TRY(st.out_off.ensure((size_t)nch * 8));
+    MGP_TRY(st.chunk_bytes.ensure((size_t)nch * 4));
+    MGP_TRY(st.dst_off.ensure((size_t)nch * 8));
+    MGP_TRY(st.sums.ensure((size_t)3 * L * 8));
+    HIP_TRY(hipMemsetAsync(st.sums.p, 0, (size_t)3 * L * 8, s));
+    std::vector<uint64_t> oo((size_t)nch);
+    for (int64_t k = 0; k < nch; ++k) oo[(size_t)k] = (uint64_t)k * stride;
+    if (nco) HIP_TRY(hipMemcpyAsync(st.coc.p, job->cell_of_col, (size_t)nco * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(st.out_off.p, oo.data(), (size_t)nch * 8, hipMemcpyHostToDevice, s));
+    H5Job jb{r.rows.c16, r.tn5.t16, r.rows.d16, L, st.coc.as<int32_t>(), nco, crow, ccol, nrc, lo, ncc,
+             st.sums.as<unsigned long long>()};
+    H5Scratch sc{st.raw.as<uint8_t>(), st.tok.as<uint32_t>(), st.out.as<uint32_t>(), st.out_off.as<uint64_t>(),
+                 st.chunk_bytes.as<uint32_t>(), chunk_raw, stride, raw_stride, h5_tok_words(chunk_raw), nullptr};
+    const bool prof = std::getenv("MGP_H5_PROF") != nullptr;
+    if (prof) {
+        MGP_TRY(st.prof.ensure((size_t)nch * 64));
+        HIP_TRY(hipMemsetAsync(st.prof.p, 0, (size_t)nch * 64, s));
+        sc.prof = st.prof.as<uint64_t>();
+    }
+    if (h5_deflate(jb, sc, s) != 0) return set_err(MGP_E_HIP, "mgp_h5_tiles: deflate kernel launch failed");
+    if (prof) {  // per-phase means over the chunks (us) and the code kernel's span, to stderr
+        // stamps: 0 start, 1 parse, 2 adler, 3 end; 4 lit/dist lengths, 5 header, 6 sizes (deflate_block)
+        std::vector<uint64_t> pr((size_t)nch * 8);
+        HIP_TRY(hipMemcpyAsync(pr.data(), st.prof.p, pr.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const int ord[7] = {0, 1, 2, 4, 5, 6, 3};  // phases in time order
+        double m[6] = {0, 0, 0, 0, 0, 0};
+        uint64_t a = UINT64_MAX, b = 0;
+        for (int64_t k = 0; k < nch; ++k) {
+            const uint64_t* q = pr.data() + k * 8;
+            for (int i = 0; i < 6; ++i) m[i] += (double)(q[ord[i + 1]] - q[ord[i]]) * 0.01;
+            a = std::min(a, q[0]);
+            b = std::max(b, q[3]);
+        }
+        std::fprintf(stderr, "[mgp_h5_tiles] %lld chunks: parse %.1f us, adler %.1f, huffman %.1f, header %.1f, "
+                     "sizes %.1f, encode %.1f us per chunk; span %.2f ms\n", (long long)nch, m[0] / nch, m[1] / nch,
+                     m[2] / nch, m[3] / nch, m[4] / nch, m[5] / nch, (b - a) * 1e-5);
+    }
+    std::vector<uint32_t> cb((size_t)nch);
+    HIP_TRY(hipMemcpyAsync(cb.data(), st.chunk_bytes.p, (size_t)nch * 4, hipMemcpyDeviceToHost, s));
+    if (job->col_sums)
+        HIP_TRY(hipMemcpyAsync(job->col_sums, st.sums.p, (size_t)3 * L * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<uint64_t> dst((size_t)nch);
+    uint64_t tot = 0;
+    for (int64_t k = 0; k < nch; ++k) {
+        dst[(size_t)k] = tot;
+        tot += cb[(size_t)k];
+        job->chunk_bytes[k] = cb[(size_t)k];
+    }
+    MGP_TRY(st.packed.ensure(tot + 64));
+    HIP_TRY(hipMemcpyAsync(st.dst_off.p, dst.data(), (size_t)nch * 8, hipMemcpyHostToDevice, s));
+    if (h5_pack(sc, nch, st.dst_off.as<uint64_t>(), st.packed.as<uint8_t>(), s) != 0)
+        return set_err(MGP_E_HIP, "mgp_h5_tiles: pack kernel launch failed");
+    HIP_TRY(hipStreamSynchronize(s));
+    st.total = tot;
+    if (total_bytes) *total_bytes = (int64_t)tot;
+    return MGP_OK;
+}
+
+int mgp_h5_tiles_fetch(mgp_ctx* ctx, uint8_t* dst, int64_t cap) {
+    int device = 0;
+    const RowJobs* jobs = ctx ? ctx_jobs(ctx, &device) : nullptr;
+    if (!ctx || (!dst && jobs->h5.total)) return set_err(MGP_E_INVALID, "null ctx/dst");
+    if (cap < (int64_t)jobs->h5.total) return set_err(MGP_E_INVALID, "mgp_h5_tiles_fetch: destination too small");
+    HIP_TRY(hipSetDevice(device));
+    if (jobs->h5.total) HIP_TRY(hipMemcpy(dst, jobs->h5.packed.p, jobs->h5.total, hipMemcpyDeviceToHost));
+    return MGP_OK;
+}
+
+int mgp_txt_gz_rows(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                    mgp_txt_gz* job, uint8_t* dst, int64_t cap, int64_t* total_bytes) {
+    const char* who = "mgp_txt_gz_rows";
+    if (!job) return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    const HostRows h{counts, nullptr, depth, n_rows, mito_len};
+    return on_rows<TxtState>(device, who, PL_COUNTS | PL_DEPTH, h,
+                             [&](TxtState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+        MGP_TRY(txt_run(st, s, rows, n_rows, job));
+        if (total_bytes) *total_bytes = (int64_t)st.total;
+        if ((int64_t)st.total > cap) return set_err(MGP_E_INVALID, std::string(who) + ": destination too small");
+        if (st.total && hipMemcpy(dst, st.packed.p, st.total, hipMemcpyDeviceToHost) != hipSuccess)
+            return set_err(MGP_E_HIP, std::string(who) + ": download failed");
+        return (int)MGP_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// mgp_variant_* / mgp_allele_freq_*: variant statistics and heteroplasmy from the count
+// rows (identify_variants / calculate_allele_freq, R/mgatk2_functions.R:282-372)
+// ---------------------------------------------------------------------------
+// MGP_VAR_PROF: the kernels' device time between two events of the call's stream, to stderr
+struct VarProf {
+    hipStream_t s;
+    hipEvent_t a = nullptr, b = nullptr;
+    explicit VarProf(hipStream_t st) : s(st) {
+        if (!std::getenv("MGP_VAR_PROF")) return;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
+        (void)hipEventRecord(a, s);
+    }
+    void stop() {
+        if (a && b) (void)hipEventRecord(b, s);
+    }
+    // (after the stream is synchronised)
+    void report(const char* who, const char* what, int64_t n, int64_t m) {
+        float ms = 0;
+        if (a && b && hipEventElapsedTime(&ms, a, b) == hipSuccess)
+            std::fprintf(stderr, "[%s] %lld x %lld %s: kernels %.3f ms\n", who, (long long)n, (long long)m, what, ms);
+    }
+    ~VarProf() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+// the job's population on the device: *cells = its list (null: rows 0..n-1), *n its size
+static int var_population(DevBuf& buf, hipStream_t s, int32_t n_rows, const mgp_variant_job* job, const char* who,
+                          const int32_t** cells, int64_t* n) {
+    if (!job || job->low_coverage_threshold < 0 || (job->cells && job->n_cells < 0))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    *n = job->cells ? job->n_cells : (int64_t)n_rows;
+    *cells = nullptr;
+    if (*n > variants::kMaxCells)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 65536 cells in one call (the exactness bound of "
+                                                         "the u64 moments); split the population and add the moments");
+    if (!job->cells) return MGP_OK;
+    for (int64_t k = 0; k < *n; ++k)
+        if (job->cells[k] < -1 || job->cells[k] >= n_rows)
+            return set_err(MGP_E_INVALID, std::string(who) + ": cell out of range");
+    MGP_TRY(buf.ensure((size_t)std::max<int64_t>(*n, 1) * 4));
+    if (*n) HIP_TRY(hipMemcpyAsync(buf.p, job->cells, (size_t)*n * 4, hipMemcpyHostToDevice, s));
+    *cells = buf.as<int32_t>();
+    return MGP_OK;
+}
+
+static int var_moments(VarState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const mgp_variant_job* job,
+                       mgp_variant_moments* out) {
+    using namespace variants;
+    const char* who = "mgp_variant_moments";
+    if (!out || !out->n_det || !out->n_conf || !out->s_total || !out->s_cov || !out->m || !out->sf || !out->sr ||
+        !out->sff || !out->srr || !out->sfr || !out->n_low || !out->s_af)
+        return set_err(MGP_E_INVALID, std::string(who) + ": null output array");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    const size_t L = (size_t)rows.L, plane = L * 4;
+    MGP_TRY(st.acc.ensure(acc_words(rows.L) * 8));
+    MGP_TRY(st.part.ensure((size_t)slabs(n) * plane * 8));
+    MGP_TRY(st.f64.ensure(plane * 8));
+    MGP_TRY(st.bad.ensure(4));
+    VarProf prof(s);
+    if (moments(rows, cells, n, (uint32_t)job->low_coverage_threshold, st.acc.as<unsigned long long>(),
+                st.part.as<double>(), st.f64.as<double>(), st.bad.as<uint32_t>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "cells x positions", n, rows.L);
+    if (bad)
+        return set_err(MGP_E_INVALID, std::string(who) + ": a fwd or rev count of the population is 2^24 or more "
+                                                         "(the exactness bound of the u64 moments)");
+    uint64_t* dst[F_N] = {out->n_det, out->n_conf, out->s_total, out->m, out->sf, out->sr, out->sff, out->srr, out->sfr};
+    const uint64_t* acc = st.acc.as<uint64_t>();
+    for (int k = 0; k < F_N; ++k) HIP_TRY(hipMemcpyAsync(dst[k], acc + k * plane, plane * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->s_cov, acc + acc_scov(rows.L), L * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->n_low, acc + acc_nlow(rows.L), L * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->s_af, st.f64.p, plane * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MGP_OK;
+}
+
+static int var_dev2(VarState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const mgp_variant_job* job,
+                    const double* mean_af, double* out_dev2) {
+    using namespace variants;
+    const char* who = "mgp_variant_dev2";
+    if (!mean_af || !out_dev2) return set_err(MGP_E_INVALID, std::string(who) + ": null mean_af / out_dev2");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    const size_t plane = (size_t)rows.L * 4;
+    MGP_TRY(st.part.ensure((size_t)slabs(n) * plane * 8));
+    MGP_TRY(st.f64.ensure(plane * 8));
+    MGP_TRY(st.mu.ensure(plane * 8));
+    HIP_TRY(hipMemcpyAsync(st.mu.p, mean_af, plane * 8, hipMemcpyHostToDevice, s));
+    VarProf prof(s);
+    if (dev2(rows, cells, n, (uint32_t)job->low_coverage_threshold, st.mu.as<double>(), st.part.as<double>(),
+             st.f64.as<double>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    HIP_TRY(hipMemcpyAsync(out_dev2, st.f64.p, plane * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "cells x positions", n, rows.L);
+    return MGP_OK;
+}
+
+static int var_allele_freq(VarState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows,
+                           const mgp_variant_job* job, int64_t n_var, const int32_t* pos, const int32_t* base,
+                           int32_t min_coverage, double* out) {
+    const char* who = "mgp_allele_freq";
+    if (n_var < 0 || min_coverage < 0 || (n_var > 0 && (!pos || !base)))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    for (int64_t v = 0; v < n_var; ++v)
+        if (pos[v] < 0 || pos[v] >= rows.L || base[v] < 0 || base[v] > 3)
+            return set_err(MGP_E_INVALID, std::string(who) + ": variant position or base out of range");
+    if (n == 0 || n_var == 0) return MGP_OK;
+    if (!out) return set_err(MGP_E_INVALID, std::string(who) + ": null output");
+    if (n_var > ((int64_t)1 << 29) / n)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^29 values in one call; split the variants");
+    const size_t vals = (size_t)n_var * (size_t)n;
+    MGP_TRY(st.pos.ensure((size_t)n_var * 4));
+    MGP_TRY(st.base.ensure((size_t)n_var * 4));
+    MGP_TRY(st.out.ensure(vals * 8));
+    HIP_TRY(hipMemcpyAsync(st.pos.p, pos, (size_t)n_var * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(st.base.p, base, (size_t)n_var * 4, hipMemcpyHostToDevice, s));
+    VarProf prof(s);
+    if (variants::gather(rows, cells, n, st.pos.as<int32_t>(), st.base.as<int32_t>(), n_var, (uint32_t)min_coverage,
+                         st.out.as<double>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    HIP_TRY(hipMemcpyAsync(out, st.out.p, vals * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "variants x cells", n_var, n);
+    return MGP_OK;
+}
+
+int mgp_variant_moments_run(mgp_ctx* ctx, const mgp_variant_job* job, mgp_variant_moments* out) {
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_variant_moments_run: no run to read", &r));
+    return var_moments(r.jobs->var, r.stream, r.rows, r.n_cells, job, out);
+}
+
+int mgp_variant_dev2_run(mgp_ctx* ctx, const mgp_variant_job* job, const double* mean_af, double* out_dev2) {
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_variant_dev2_run: no run to read", &r));
+    return var_dev2(r.jobs->var, r.stream, r.rows, r.n_cells, job, mean_af, out_dev2);
+}
+
+int mgp_allele_freq_run(mgp_ctx* ctx, const mgp_variant_job* job, int64_t n_var, const int32_t* pos,
+                        const int32_t* base, int32_t min_coverage, double* out) {
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_allele_freq_run: no run to read", &r));
+    return var_allele_freq(r.jobs->var, r.stream, r.rows, r.n_cells, job, n_var, pos, base, min_coverage, out);
+}
+
+int mgp_variant_moments_rows(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                             const mgp_variant_job* job, mgp_variant_moments* out) {
+    const HostRows h{counts, nullptr, depth, n_rows, mito_len};
+    return on_rows<VarState>(device, "mgp_variant_moments_rows", PL_COUNTS | PL_DEPTH, h,
+                             [&](VarState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+        return var_moments(st, s, rows, n_rows, job, out);
+    });
+}
+
+int mgp_variant_dev2_rows(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                          const mgp_variant_job* job, const double* mean_af, double* out_dev2) {
+    const HostRows h{counts, nullptr, depth, n_rows, mito_len};
+    return on_rows<VarState>(device, "mgp_variant_dev2_rows", PL_COUNTS | PL_DEPTH, h,
+                             [&](VarState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+        return var_dev2(st, s, rows, n_rows, job, mean_af, out_dev2);
+    });
+}
+
+int mgp_allele_freq_rows(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                         const mgp_variant_job* job, int64_t n_var, const int32_t* pos, const int32_t* base,
+                         int32_t min_coverage, double* out) {
+    const HostRows h{counts, nullptr, depth, n_rows, mito_len};
+    return on_rows<VarState>(device, "mgp_allele_freq_rows", PL_COUNTS | PL_DEPTH, h,
+                             [&](VarState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+        return var_allele_freq(st, s, rows, n_rows, job, n_var, pos, base, min_coverage, out);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// mgp_cell_coverage_* / mgp_position_*: coverage QC from the count rows
+// (calculate_cell_coverage_stats ... calculate_transposition_stats, R/mgatk2_functions.R:138-280)
+// ---------------------------------------------------------------------------
+static int qc_sum_bounds(const txtgz::Rows& rows, const char* who) {
+    if (rows.L > qc::kMaxL)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 65536 positions (the exactness bound of the u64 sums)");
+    return MGP_OK;
+}
+
+static int qc_bad(QcState& st, hipStream_t s, const char* who) {
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad)
+        return set_err(MGP_E_INVALID, std::string(who) + ": a depth or count of the population is 2^24 or more (the "
+                                                         "exactness bound of the u64 sums)");
+    return MGP_OK;
+}
+
+static int qc_cell_coverage(QcState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows,
+                            const mgp_variant_job* job, mgp_cell_coverage* out) {
+    using namespace qc;
+    const char* who = "mgp_cell_coverage";
+    if (!out) return set_err(MGP_E_INVALID, std::string(who) + ": null output");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    MGP_TRY(qc_sum_bounds(rows, who));
+    if (n == 0) return MGP_OK;
+    if (!out->s_depth || !out->s_depth2 || !out->max_depth || !out->n_covered || !out->n_10x || !out->n_50x ||
+        !out->mid_lo || !out->mid_hi)
+        return set_err(MGP_E_INVALID, std::string(who) + ": null output array");
+    MGP_TRY(st.out64.ensure((size_t)n * CELL64_N * 8));
+    MGP_TRY(st.out32.ensure((size_t)n * CELL32_N * 4));
+    MGP_TRY(st.bad.ensure(4));
+    VarProf prof(s);
+    if (cell_stats(rows, cells, n, st.out64.as<unsigned long long>(), st.out32.as<uint32_t>(), st.bad.as<uint32_t>(),
+                   s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    MGP_TRY(qc_bad(st, s, who));
+    prof.report(who, "cells x positions", n, rows.L);
+    std::vector<uint64_t> h64((size_t)n * CELL64_N);
+    std::vector<uint32_t> h32((size_t)n * CELL32_N);
+    HIP_TRY(hipMemcpyAsync(h64.data(), st.out64.p, h64.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h32.data(), st.out32.p, h32.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    uint32_t* dst32[CELL32_N] = {out->max_depth, out->n_covered, out->n_10x, out->n_50x, out->mid_lo, out->mid_hi};
+    for (int64_t k = 0; k < n; ++k) {
+        out->s_depth[k] = h64[k * CELL64_N + CELL64_SD];
+        out->s_depth2[k] = h64[k * CELL64_N + CELL64_SD2];
+        for (int f = 0; f < CELL32_N; ++f) dst32[f][k] = h32[k * CELL32_N + f];
+    }
+    return MGP_OK;
+}
+
+static int qc_position_coverage(QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5& tn5,
+                                int32_t n_rows, const mgp_variant_job* job, mgp_position_coverage* out) {
+    using namespace qc;
+    const char* who = "mgp_position_coverage";
+    if (!out || !out->s_depth || !out->s_depth2 || !out->s_fwd || !out->s_rev || !out->s_tn5_fwd || !out->s_tn5_rev ||
+        !out->tally || !out->n_covered || !out->n_10x || !out->n_50x || !out->n_tn5 || !out->max_depth)
+        return set_err(MGP_E_INVALID, std::string(who) + ": null output array");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    MGP_TRY(qc_sum_bounds(rows, who));
+    const size_t L = (size_t)rows.L;
+    MGP_TRY(st.out64.ensure(L * POS64_N * 8));
+    MGP_TRY(st.out32.ensure(L * POS32_N * 4));
+    MGP_TRY(st.bad.ensure(4));
+    VarProf prof(s);
+    if (pos_stats(rows, tn5, cells, n, st.out64.as<unsigned long long>(), st.out32.as<uint32_t>(),
+                  st.bad.as<uint32_t>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    MGP_TRY(qc_bad(st, s, who));
+    prof.report(who, "cells x positions", n, rows.L);
+    uint64_t* dst64[POS64_TALLY] = {out->s_depth, out->s_depth2, out->s_fwd, out->s_rev, out->s_tn5_fwd, out->s_tn5_rev};
+    uint32_t* dst32[POS32_N] = {out->n_covered, out->n_10x, out->n_50x, out->n_tn5, out->max_depth};
+    const uint64_t* a64 = st.out64.as<uint64_t>();
+    const uint32_t* a32 = st.out32.as<uint32_t>();
+    for (int f = 0; f < POS64_TALLY; ++f) HIP_TRY(hipMemcpyAsync(dst64[f], a64 + f * L, L * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->tally, a64 + POS64_TALLY * L, L * 4 * 8, hipMemcpyDeviceToHost, s));
+    for (int f = 0; f < POS32_N; ++f) HIP_TRY(hipMemcpyAsync(dst32[f], a32 + f * L, L * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MGP_OK;
+}
+
+static int qc_depth_hist(QcState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const mgp_variant_job* job,
+                         int32_t shift, const uint32_t* prefix, uint32_t* hist) {
+    const char* who = "mgp_position_depth_hist";
+    if (!hist || (shift != 0 && shift != 8 && shift != 16 && shift != 24) || (shift != 24 && !prefix))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments (shift is 0, 8, 16 or 24)");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    const size_t L = (size_t)rows.L;
+    MGP_TRY(st.in32.ensure(L * 4));
+    MGP_TRY(st.hist.ensure(L * 256 * 4));
+    if (shift != 24) HIP_TRY(hipMemcpyAsync(st.in32.p, prefix, L * 4, hipMemcpyHostToDevice, s));
+    VarProf prof(s);
+    if (qc::pos_depth_hist(rows, cells, n, shift, st.in32.as<uint32_t>(), st.hist.as<uint32_t>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    HIP_TRY(hipMemcpyAsync(hist, st.hist.p, L * 256 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "cells x positions", n, rows.L);
+    return MGP_OK;
+}
+
+static int qc_depth_next(QcState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const mgp_variant_job* job,
+                         const uint32_t* v, uint32_t* n_le, uint32_t* next) {
+    const char* who = "mgp_position_depth_next";
+    if (!v || !n_le || !next) return set_err(MGP_E_INVALID, std::string(who) + ": null array");
+    const int32_t* cells = nullptr;
+    int64_t n = 0;
+    MGP_TRY(var_population(st.cells, s, n_rows, job, who, &cells, &n));
+    const size_t L = (size_t)rows.L;
+    MGP_TRY(st.in32.ensure(L * 4));
+    MGP_TRY(st.out32.ensure(L * 2 * 4));
+    HIP_TRY(hipMemcpyAsync(st.in32.p, v, L * 4, hipMemcpyHostToDevice, s));
+    uint32_t* o = st.out32.as<uint32_t>();
+    VarProf prof(s);
+    if (qc::pos_depth_next(rows, cells, n, st.in32.as<uint32_t>(), o, o + L, s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    prof.stop();
+    HIP_TRY(hipMemcpyAsync(n_le, o, L * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(next, o + L, L * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "cells x positions", n, rows.L);
+    return MGP_OK;
+}
+
+int mgp_cell_coverage_run(mgp_ctx* ctx, const mgp_variant_job* job, mgp_cell_coverage* out) {
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_cell_coverage_run: no run to read", &r));
+    return qc_cell_coverage(r.jobs->qc, r.stream, r.rows, r.n_cells, job, out);
+}
+
+int mgp_position_coverage_run(mgp_ctx* ctx, const mgp_variant_job* job, mgp_position_coverage* out) {
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_position_coverage_run: no run to read", &r));
+    return qc_position_coverage(r.jobs->qc, r.stream, r.rows, r.tn5, r.n_cells, job, out);
+}
+
+int mgp_position_depth_hist_run(mgp_ctx* ctx, const mgp_variant_job* job, int32_t shift, const uint32_t* prefix,
+                                uint32_t* hist) {
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_position_depth_hist_run: no run to read", &r));
+    return qc_depth_hist(r.jobs->qc, r.stream, r.rows, r.n_cells, job, shift, prefix, hist);
+}
+
+int mgp_position_depth_next_run(mgp_ctx* ctx, const mgp_variant_job* job, const uint32_t* v, uint32_t* n_le,
+                                uint32_t* next) {
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_position_depth_next_run: no run to read", &r));
+    return qc_depth_next(r.jobs->qc, r.stream, r.rows, r.n_cells, job, v, n_le, next);
+}
+
+int mgp_cell_coverage_rows(int device, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                           const mgp_variant_job* job, mgp_cell_coverage* out) {
+    const HostRows h{nullptr, nullptr, depth, n_rows, mito_len};
+    return on_rows<QcState>(device, "mgp_cell_coverage_rows", PL_DEPTH, h,
+                            [&](QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+        return qc_cell_coverage(st, s, rows, n_rows, job, out);
+    });
+}
+
+int mgp_position_coverage_rows(int device, const uint32_t* counts, const uint32_t* tn5, const uint32_t* depth,
+                               int32_t n_rows, int32_t mito_len, const mgp_variant_job* job,
+                               mgp_position_coverage* out) {
+    const HostRows h{counts, tn5, depth, n_rows, mito_len};
+    return on_rows<QcState>(device, "mgp_position_coverage_rows", PL_COUNTS | PL_TN5 | PL_DEPTH, h,
+                            [&](QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5& t) {
+        return qc_position_coverage(st, s, rows, t, n_rows, job, out);
+    });
+}
+
+int mgp_position_depth_hist_rows(int device, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                                 const mgp_variant_job* job, int32_t shift, const uint32_t* prefix, uint32_t* hist) {
+    const HostRows h{nullptr, nullptr, depth, n_rows, mito_len};
+    return on_rows<QcState>(device, "mgp_position_depth_hist_rows", PL_DEPTH, h,
+                            [&](QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+        return qc_depth_hist(st, s, rows, n_rows, job, shift, prefix, hist);
+    });
+}
+
+int mgp_position_depth_next_rows(int device, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                                 const mgp_variant_job* job, const uint32_t* v, uint32_t* n_le, uint32_t* next) {
+    const HostRows h{nullptr, nullptr, depth, n_rows, mito_len};
+    return on_rows<QcState>(device, "mgp_position_depth_next_rows", PL_DEPTH, h,
+                            [&](QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+        return qc_depth_next(st, s, rows, n_rows, job, v, n_le, next);
+    });
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// mgp_qc.h — coverage QC on the device (internal interface between mgp_engine.hip and
+// mgp_qc.h — coverage QC on the device (internal interface between mgp_jobs.hip and
 // mgp_qc.hip; the C-ABI is mgp_cell_coverage_* / mgp_position_* in include/mgpileup.h).
 //
 // The front half of mgatk's downstream workflow (calculate_cell_coverage_stats,

@@ -1,5 +1,5 @@
 // mgp_txtgz.h — the engine's txt writer on the device (internal interface between
-// mgp_engine.hip and mgp_txtgz.hip; the C-ABI is mgp_txt_gz* in include/mgpileup.h).
+// mgp_jobs.hip and mgp_txtgz.hip; the C-ABI is mgp_txt_gz* in include/mgpileup.h).
 //
 // IncrementalTextWriter (src/file_io/writers.py:430-486) formats, per passing cell,
 //   output.coverage.txt: "pos,barcode,depth\n"   for every position with depth > 0

@@ -1,5 +1,5 @@
 // mgp_variants.h — variant statistics and heteroplasmy on the device (internal interface
-// between mgp_engine.hip and mgp_variants.hip; the C-ABI is mgp_variant_* / mgp_allele_freq_*
+// between mgp_jobs.hip and mgp_variants.hip; the C-ABI is mgp_variant_* / mgp_allele_freq_*
 // in include/mgpileup.h).
 //
 // mgatk's variant calling (identify_variants / calculate_allele_freq, R over counts.h5)

@@ -192,3 +192,54 @@ def test_batch_struct_optional_columns():
     full = batch_struct(soa)
     assert full.span == soa.span.ctypes.data and full.rec_off == soa.rec_off.ctypes.data
     assert np.all(soa.span >= 50)
+
+
+def test_row_jobs_refuse_null_arguments_before_any_device_call():
+    """The detached (*_rows) entry points refuse a missing plane of those they read, and the
+    *_run forms a null context, with MGP_E_INVALID and their own message, before any device
+    call (so this runs without a device). Planes read: depth alone for the cell coverage and
+    the two depth passes, counts + tn5 + depth for the position coverage, counts + depth for
+    the txt writer and the variant forms."""
+    from mgatk2_amd import engine
+    from mgatk2_amd.build import build_engine
+
+    build_engine()
+    lib = engine.load_library()
+    n_rows, mito_len = 1, 8
+    planes = {"counts": np.zeros((n_rows, mito_len, 8), np.uint32), "tn5": np.zeros((n_rows, mito_len, 2), np.uint32),
+              "depth": np.zeros((n_rows, mito_len), np.uint32)}
+    job = engine.mgp_txt_gz()
+
+    def refused(name, message, *args):
+        rc = getattr(lib, name)(*args)
+        assert rc == engine.MGP_E_INVALID, (name, args, rc)
+        assert lib.mgp_last_error().decode() == message, (name, args)
+
+    # name -> (the planes it takes, in argument order; the arguments after mito_len)
+    detached = {
+        "mgp_txt_gz_rows": (("counts", "depth"), (job, None, 0, None)),
+        "mgp_variant_moments_rows": (("counts", "depth"), (None, None)),
+        "mgp_variant_dev2_rows": (("counts", "depth"), (None, None, None)),
+        "mgp_allele_freq_rows": (("counts", "depth"), (None, 0, None, None, 0, None)),
+        "mgp_cell_coverage_rows": (("depth",), (None, None)),
+        "mgp_position_coverage_rows": (("counts", "tn5", "depth"), (None, None)),
+        "mgp_position_depth_hist_rows": (("depth",), (None, 24, None, None)),
+        "mgp_position_depth_next_rows": (("depth",), (None, None, None, None)),
+    }
+    assert set(detached) == {s for s in engine.ABI_SYMBOLS if s.endswith("_rows")}
+    for name, (takes, rest) in detached.items():
+        for missing in takes:
+            ptrs = [None if p == missing else planes[p].ctypes.data for p in takes]
+            refused(name, f"{name}: bad arguments", 0, *ptrs, n_rows, mito_len, *rest)
+    refused("mgp_txt_gz_rows", "mgp_txt_gz_rows: bad arguments", 0, planes["counts"].ctypes.data,
+            planes["depth"].ctypes.data, n_rows, 0, job, None, 0, None)
+
+    refused("mgp_txt_gz_run", "null ctx/job", None, job, None)
+    refused("mgp_h5_tiles_run", "null ctx/job", None, engine.mgp_h5_tiles(), None)
+    refused("mgp_variant_moments_run", "null ctx", None, None, None)
+    refused("mgp_variant_dev2_run", "null ctx", None, None, None, None)
+    refused("mgp_allele_freq_run", "null ctx", None, None, 0, None, None, 0, None)
+    refused("mgp_cell_coverage_run", "null ctx", None, None, None)
+    refused("mgp_position_coverage_run", "null ctx", None, None, None)
+    refused("mgp_position_depth_hist_run", "null ctx", None, None, 24, None, None)
+    refused("mgp_position_depth_next_run", "null ctx", None, None, None, None, None)
