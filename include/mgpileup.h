@@ -65,7 +65,9 @@ extern "C" {
                                  (variant statistics and heteroplasmy on the device),
                                  mgp_cell_coverage_*, mgp_position_coverage_*,
                                  mgp_position_depth_hist_*, mgp_position_depth_next_*
-                                 (coverage QC on the device) */
+                                 (coverage QC on the device),
+                                 mgp_pair_dist, mgp_hclust_dist, mgp_hclust (clustering by
+                                 heteroplasmy on the device) */
 
 /* ---- return codes (0 = success) ------------------------------------------ */
 #define MGP_OK               0
@@ -707,6 +709,35 @@ int  mgp_position_depth_hist_rows(int device, const uint32_t *depth, int32_t n_r
                                   const mgp_variant_job *job, int32_t shift, const uint32_t *prefix, uint32_t *hist);
 int  mgp_position_depth_next_rows(int device, const uint32_t *depth, int32_t n_rows, int32_t mito_len,
                                   const mgp_variant_job *job, const uint32_t *v, uint32_t *n_le, uint32_t *next);
+/* Clustering by heteroplasmy on the device (added under ABI 7). Replaces the step of mgatk's
+ * vignette after calculate_allele_freq, pheatmap's dist(..., "euclidean") and
+ * hclust(..., "complete") over the cells and over the variants of the heteroplasmy matrix
+ * (R/mgatk2_qc_plots.R:121-139). No engine context: the calls run on `device` with buffers
+ * of their own, all freed on return (MGP_E_OOM leaves nothing allocated).
+ * Items are the columns of x [n_feat][n_items], fp64, feature-major (mgp_allele_freq_*'s
+ * layout with cells as items). Every value must be finite, otherwise MGP_E_INVALID.
+ * Distance: D[i][j] = sqrt(sum_k (x[k][i] - x[k][j])^2) in fp64; one thread sums a pair in
+ * ascending k with s = fma(d, d, s), so the bytes depend on the input alone; D is exactly
+ * symmetric, D[i][i] = 0 and equal columns are at exactly 0.
+ * Linkage: complete linkage on D as R's hclust does it. Clusters are named by their lowest
+ * member; each of the n - 1 steps merges the active pair i < j of smallest distance (ties:
+ * smallest i, then smallest j) into i and sets D(i, k) = max(D(i, k), D(j, k)). It only
+ * compares and selects: given D, every output is exact.
+ * Outputs in R's hclust conventions, 1-based: merge [n_items - 1][2] (item i as -(i + 1), the
+ * cluster made at step s as s; a singleton before a cluster, two singletons by item, two
+ * clusters by step), height [n_items - 1] (non-decreasing), order [n_items] (the last merge's
+ * pair with every cluster replaced in place by its own pair). n_items == 1: order = {1};
+ * n_items == 0: nothing is written or launched.
+ * Bounds: n_items <= 65,536 and n_feat <= 2^24, otherwise MGP_E_INVALID before any
+ * allocation. Device memory: 8 n^2 + 8 n n_feat + 33 n bytes (32 GiB of D at the bound). */
+int  mgp_pair_dist(int device, const double *x, int64_t n_items, int64_t n_feat, double *out_dist /* [n][n] */);
+/* Linkage alone from the caller's matrix dist [n][n]: symmetric, finite, >= 0 (checked on
+ * the device before the linkage: MGP_E_INVALID otherwise). */
+int  mgp_hclust_dist(int device, const double *dist, int64_t n_items, int32_t *merge, double *height,
+                     int32_t *order);
+/* Both; the matrix stays on the device unless out_dist [n][n] is given (it may be NULL). */
+int  mgp_hclust(int device, const double *x, int64_t n_items, int64_t n_feat, int32_t *merge, double *height,
+                int32_t *order, double *out_dist);
 /* Position windows of the pileup (the `wide` flags' second dimension). */
 int  mgp_windows(mgp_ctx *ctx, int32_t *n_windows, int32_t *window_width);
 /* Wait until the H2D copies of every batch pushed so far have completed: the caller may

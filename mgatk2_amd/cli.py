@@ -5,7 +5,9 @@ reference command line runs unchanged (``python -m mgatk2_amd run -i ...``).
 Added: ``--device`` (HIP device ordinal for the engine), ``--variants`` with its
 ``--variant-*`` thresholds (variant calling from the device's rows, variants/ in the output),
 and ``--coverage-stats`` / ``--cell-min-mean-coverage`` / ``--cell-min-coverage-breadth`` /
-``--recompute-reference`` (coverage QC and the cell filter from the device's rows, coverage/).
+``--recompute-reference`` (coverage QC and the cell filter from the device's rows, coverage/),
+and ``--cluster`` / ``--clones K`` (the heteroplasmy matrix's cells and variants clustered on
+the device, the trees and heatmap orders in variants/).
 Not carried over: ``hardmask-fasta`` (FASTA masking utility, outside the hot path).
 """
 
@@ -57,6 +59,11 @@ def _variant_options(f):
                      help="Keep cells with at least this fraction of positions covered"),
         click.option("--recompute-reference", is_flag=True,
                      help="Reference alleles from the kept cells (coverage/reference_alleles.tsv; used by --variants)"),
+        click.option("--cluster", is_flag=True,
+                     help="Cluster cells and variants by heteroplasmy on the device (Euclidean, complete linkage): "
+                          "variants/{cell,variant}_{hclust,order}.tsv; needs --variants"),
+        click.option("--clones", default=None, type=click.IntRange(min=1), metavar="K",
+                     help="Cut the cell tree into K clones (variants/cell_clones.tsv); needs --cluster"),
     ]
     for o in reversed(opts):
         f = o(f)
@@ -65,10 +72,17 @@ def _variant_options(f):
 
 def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
                   variant_low_coverage, variant_min_coverage, coverage_stats=False, cell_min_mean_coverage=0.0,
-                  cell_min_coverage_breadth=0.0, recompute_reference=False) -> dict:
+                  cell_min_coverage_breadth=0.0, recompute_reference=False, cluster=False, clones=None) -> dict:
     """The options run_pipeline gets beyond the reference's, each only when asked for: the
     variant options with --variants; the four coverage options with --coverage-stats,
-    otherwise the filter thresholds and --recompute-reference that were given."""
+    otherwise the filter thresholds and --recompute-reference that were given; --cluster and
+    --clones when given (--cluster needs --variants, --clones needs --cluster: a usage error)."""
+    if cluster and not call_variants:
+        raise click.UsageError("--cluster requires --variants")
+    if clones is not None and not cluster:
+        raise click.UsageError("--clones requires --cluster")
+    if clones is not None and int(clones) < 1:
+        raise click.UsageError("--clones must be at least 1")
     out = {}
     if call_variants:
         out.update(call_variants=call_variants, variant_min_cells=variant_min_cells,
@@ -82,6 +96,10 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
         out.update(coverage_stats=True, **cov)
     else:
         out.update({k: v for k, v in cov.items() if v})
+    if cluster:
+        out.update(cluster=True)
+        if clones is not None:
+            out.update(clones=int(clones))
     return out
 
 
@@ -290,6 +308,8 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
                         variant_args.get("coverage_stats", False), variant_args.get("cell_min_mean_coverage", 0.0),
                         variant_args.get("cell_min_coverage_breadth", 0.0),
                         variant_args.get("recompute_reference", False))
+        if variant_args and variant_args.get("cluster"):
+            logger.info("  Clustering:             complete linkage, clones %s", variant_args.get("clones"))
         if dry_run:
             return 0
         if report_title is None:
@@ -398,6 +418,7 @@ def tenx(bam_path, mito_genome, barcode_file, barcode_tag, min_barcode_reads, ou
 def call(bam_path, mito_genome, output_dir, ncores, verbose, max_memory, base_qual, min_mapq, max_strand_bias,
          min_distance_from_end, dedup_mode, output_format, dry_run, device, **variant_kw):
     """Run mgatk2 and treat each bam file as a single cell (commands/call.py)"""
+    variant_args = _variant_args(**variant_kw)
     bam_files = sorted(Path(bam_path).glob("*.bam"))
     if not bam_files:
         logger.error(f"No BAM files (*.bam) found in directory: {bam_path}")
@@ -412,7 +433,7 @@ def call(bam_path, mito_genome, output_dir, ncores, verbose, max_memory, base_qu
         logger.info(f"[{i}/{len(bam_files)}] Processing: {bam_file.name} -> {out}")
         run_pipeline_command(str(bam_file), str(out), None, "CB", 10, mito_chr, ncores, verbose, 1, max_memory,
                              base_qual, min_mapq, 0, max_strand_bias, min_distance_from_end, dedup_mode, output_format,
-                             ncores == 1, dry_run=False, device=device, variant_args=_variant_args(**variant_kw))
+                             ncores == 1, dry_run=False, device=device, variant_args=variant_args)
     logger.info("Analysis completed for all %s BAM files", len(bam_files))
 
 

@@ -3,7 +3,8 @@
 // mgp_txtgz.hip), the variant statistics (mgp_variants.hip) and the coverage QC passes
 // (mgp_qc.hip). Each job has two forms: *_run on a context's last run, whose rows it gets
 // through run_rows (mgp_jobs.h: the context itself is opaque here), and the detached
-// *_rows form on u32 rows of the caller's (on_rows).
+// *_rows form on u32 rows of the caller's (on_rows). The clustering of the heteroplasmy
+// matrix (mgp_cluster.hip) reads no rows and needs no context: mgp_pair_dist / mgp_hclust*.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../../include/mgpileup.h"
+#include "mgp_cluster.h"
 #include "mgp_host.h"
 #include "mgp_jobs.h"
 #include "mgp_qc.h"
@@ -45,6 +47,11 @@ struct VarState {
 // mgp_cell_coverage_* / mgp_position_*: the coverage QC passes' buffers (mgp_qc.hip)
 struct QcState {
     DevBuf cells, out64, out32, bad, in32, hist;
+};
+
+// mgp_pair_dist / mgp_hclust*: the clustering's buffers (mgp_cluster.hip), a call's own
+struct ClusterState {
+    DevBuf x, dist, bad, nn, dnn, act, list, si, sj, sh;
 };
 
 struct RowJobs {
@@ -91,6 +98,23 @@ static int on_rows(int device, const char* who, int need, const HostRows& h, Job
                                mito_len, 1};
         const qc::Tn5 t{nullptr, buf[1].as<uint32_t>()};
         if (rc == MGP_OK) rc = job(st, s, rows, t);
+        (void)hipStreamSynchronize(s);
+    }
+    (void)hipStreamDestroy(s);
+    return rc;
+}
+
+// The clustering calls: job(state, stream) on `device` with a stream and a ClusterState of
+// the call's own, freed once that stream is idle.
+template <class Job>
+static int cl_call(int device, Job&& job) {
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    int rc;
+    {
+        ClusterState st;
+        rc = job(st, s);
         (void)hipStreamSynchronize(s);
     }
     (void)hipStreamDestroy(s);
@@ -763,6 +787,154 @@ int mgp_position_depth_next_rows(int device, const uint32_t* depth, int32_t n_ro
     return on_rows<QcState>(device, "mgp_position_depth_next_rows", PL_DEPTH, h,
                             [&](QcState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
         return qc_depth_next(st, s, rows, n_rows, job, v, n_le, next);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// mgp_pair_dist / mgp_hclust_dist / mgp_hclust: Euclidean pair distances and complete
+// linkage of the heteroplasmy matrix's columns (pheatmap's dist() + hclust(), the step
+// after calculate_allele_freq in R/mgatk2_qc_plots.R:121-139). No engine context: a call
+// has its own stream and buffers, all freed when it returns (also when it fails).
+// ---------------------------------------------------------------------------
+// the checks before any device call: negative sizes, the bounds, then a missing array
+static int cl_args(const char* who, int64_t n, int64_t nf, bool missing) {
+    if (n < 0 || nf < 0) return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    if (n > cluster::kMaxItems)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 65536 items in one call (the distance matrix "
+                                                         "is 8 n^2 bytes)");
+    if (nf > cluster::kMaxFeat) return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^24 features in one call");
+    if (missing) return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    return MGP_OK;
+}
+
+// the `bad` word of the kernels, after the stream is idle
+static int cl_bad(ClusterState& st, hipStream_t s, uint32_t* bad) {
+    HIP_TRY(hipMemcpyAsync(bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MGP_OK;
+}
+
+// st.dist [n][n] from the host's x [nf][n]; refuses a value that is not finite
+static int cl_dist(ClusterState& st, hipStream_t s, const char* who, const double* x, int64_t n, int64_t nf) {
+    MGP_TRY(st.dist.ensure((size_t)n * (size_t)n * 8));
+    MGP_TRY(st.x.ensure(std::max<size_t>((size_t)n * (size_t)nf * 8, 8)));
+    MGP_TRY(st.bad.ensure(4));
+    if (nf) HIP_TRY(hipMemcpyAsync(st.x.p, x, (size_t)n * (size_t)nf * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(st.bad.p, 0, 4, s));
+    VarProf prof(s);
+    if (cluster::pair_dist(st.x.as<double>(), (int)n, (int)nf, st.dist.as<double>(), st.bad.as<uint32_t>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": distance kernel launch failed");
+    prof.stop();
+    uint32_t bad = 0;
+    MGP_TRY(cl_bad(st, s, &bad));
+    prof.report(who, "items x features, pair distances", n, nf);
+    if (bad) return set_err(MGP_E_INVALID, std::string(who) + ": a value of x is not finite");
+    return MGP_OK;
+}
+
+// R's merge and order from the n - 1 raw steps (i < j, clusters named by their lowest member)
+static void cl_tree(int64_t n, const int32_t* si, const int32_t* sj, int32_t* merge, int32_t* order) {
+    std::vector<int32_t> lab((size_t)n);
+    for (int64_t k = 0; k < n; ++k) lab[(size_t)k] = -(int32_t)(k + 1);
+    for (int64_t s = 0; s + 1 < n; ++s) {
+        int32_t a = lab[(size_t)si[s]], b = lab[(size_t)sj[s]];
+        // a singleton before a cluster; two singletons by item (i < j); two clusters by step
+        if ((a > 0 && b < 0) || (a > 0 && b > 0 && b < a)) std::swap(a, b);
+        merge[2 * s] = a;
+        merge[2 * s + 1] = b;
+        lab[(size_t)si[s]] = (int32_t)(s + 1);
+    }
+    // the last merge's pair, every cluster replaced in place by its own pair: depth first, left to right
+    std::vector<int32_t> stack;
+    int64_t out = 0;
+    if (n == 1) order[out++] = 1;
+    if (n >= 2) stack.push_back((int32_t)(n - 1));
+    while (!stack.empty()) {
+        const int32_t e = stack.back();
+        stack.pop_back();
+        if (e < 0) {
+            order[out++] = -e;
+        } else {
+            stack.push_back(merge[2 * (e - 1) + 1]);
+            stack.push_back(merge[2 * (e - 1)]);
+        }
+    }
+}
+
+// the linkage on st.dist (overwritten), then merge / height / order on the host
+static int cl_link(ClusterState& st, hipStream_t s, const char* who, int64_t n, int32_t* merge, double* height,
+                   int32_t* order) {
+    std::vector<int32_t> si((size_t)std::max<int64_t>(n - 1, 0)), sj(si.size());
+    if (n >= 2) {
+        MGP_TRY(st.nn.ensure((size_t)n * 4));
+        MGP_TRY(st.dnn.ensure((size_t)n * 8));
+        MGP_TRY(st.act.ensure((size_t)n));
+        MGP_TRY(st.list.ensure((size_t)n * 4));
+        MGP_TRY(st.si.ensure((size_t)n * 4));
+        MGP_TRY(st.sj.ensure((size_t)n * 4));
+        MGP_TRY(st.sh.ensure((size_t)n * 8));
+        VarProf prof(s);
+        if (cluster::linkage(st.dist.as<double>(), (int)n, st.nn.as<int32_t>(), st.dnn.as<double>(), st.act.as<uint8_t>(),
+                             st.list.as<int32_t>(), st.si.as<int32_t>(), st.sj.as<int32_t>(), st.sh.as<double>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": linkage kernel launch failed");
+        prof.stop();
+        HIP_TRY(hipMemcpyAsync(si.data(), st.si.p, (size_t)(n - 1) * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(sj.data(), st.sj.p, (size_t)(n - 1) * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(height, st.sh.p, (size_t)(n - 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        prof.report(who, "items, linkage steps", n, n - 1);
+        for (int64_t k = 0; k + 1 < n; ++k)
+            if (si[(size_t)k] < 0 || sj[(size_t)k] <= si[(size_t)k] || sj[(size_t)k] >= n)
+                return set_err(MGP_E_HIP, std::string(who) + ": the linkage returned an invalid step");
+    }
+    cl_tree(n, si.data(), sj.data(), merge, order);
+    return MGP_OK;
+}
+
+int mgp_pair_dist(int device, const double* x, int64_t n_items, int64_t n_feat, double* out_dist) {
+    const char* who = "mgp_pair_dist";
+    MGP_TRY(cl_args(who, n_items, n_feat, n_items > 0 && (!out_dist || (n_feat > 0 && !x))));
+    if (n_items == 0) return MGP_OK;
+    return cl_call(device, [&](ClusterState& st, hipStream_t s) {
+        MGP_TRY(cl_dist(st, s, who, x, n_items, n_feat));
+        HIP_TRY(hipMemcpyAsync(out_dist, st.dist.p, (size_t)n_items * (size_t)n_items * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return (int)MGP_OK;
+    });
+}
+
+int mgp_hclust_dist(int device, const double* dist, int64_t n_items, int32_t* merge, double* height, int32_t* order) {
+    const char* who = "mgp_hclust_dist";
+    MGP_TRY(cl_args(who, n_items, 0, (n_items > 0 && (!dist || !order)) || (n_items > 1 && (!merge || !height))));
+    if (n_items == 0) return MGP_OK;
+    return cl_call(device, [&](ClusterState& st, hipStream_t s) {
+        const size_t bytes = (size_t)n_items * (size_t)n_items * 8;
+        MGP_TRY(st.dist.ensure(bytes));
+        MGP_TRY(st.bad.ensure(4));
+        HIP_TRY(hipMemcpyAsync(st.dist.p, dist, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(st.bad.p, 0, 4, s));
+        if (cluster::check_dist(st.dist.as<double>(), (int)n_items, st.bad.as<uint32_t>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": check kernel launch failed");
+        uint32_t bad = 0;
+        MGP_TRY(cl_bad(st, s, &bad));
+        if (bad & cluster::BAD_VALUE)
+            return set_err(MGP_E_INVALID, std::string(who) + ": a distance is negative or not finite");
+        if (bad) return set_err(MGP_E_INVALID, std::string(who) + ": the distance matrix is not symmetric");
+        return cl_link(st, s, who, n_items, merge, height, order);
+    });
+}
+
+int mgp_hclust(int device, const double* x, int64_t n_items, int64_t n_feat, int32_t* merge, double* height,
+               int32_t* order, double* out_dist) {
+    const char* who = "mgp_hclust";
+    MGP_TRY(cl_args(who, n_items, n_feat,
+                    (n_items > 0 && (!order || (n_feat > 0 && !x))) || (n_items > 1 && (!merge || !height))));
+    if (n_items == 0) return MGP_OK;
+    return cl_call(device, [&](ClusterState& st, hipStream_t s) {
+        MGP_TRY(cl_dist(st, s, who, x, n_items, n_feat));
+        if (out_dist)  // (before the linkage overwrites the matrix)
+            HIP_TRY(hipMemcpyAsync(out_dist, st.dist.p, (size_t)n_items * (size_t)n_items * 8, hipMemcpyDeviceToHost, s));
+        return cl_link(st, s, who, n_items, merge, height, order);
     });
 }
 

@@ -44,7 +44,7 @@ ABI_SYMBOLS = (
     "mgp_allele_freq_run", "mgp_variant_moments_rows", "mgp_variant_dev2_rows", "mgp_allele_freq_rows",
     "mgp_cell_coverage_run", "mgp_position_coverage_run", "mgp_position_depth_hist_run",
     "mgp_position_depth_next_run", "mgp_cell_coverage_rows", "mgp_position_coverage_rows",
-    "mgp_position_depth_hist_rows", "mgp_position_depth_next_rows",
+    "mgp_position_depth_hist_rows", "mgp_position_depth_next_rows", "mgp_pair_dist", "mgp_hclust_dist", "mgp_hclust",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -310,6 +310,9 @@ def load_library(path: Path | None = None) -> C.CDLL:
         ),
         "mgp_position_depth_hist_rows": ([C.c_int, vp, i32, i32, C.POINTER(mgp_variant_job), i32, vp, vp], C.c_int),
         "mgp_position_depth_next_rows": ([C.c_int, vp, i32, i32, C.POINTER(mgp_variant_job), vp, vp, vp], C.c_int),
+        "mgp_pair_dist": ([C.c_int, vp, i64, i64, vp], C.c_int),
+        "mgp_hclust_dist": ([C.c_int, vp, i64, vp, vp, vp], C.c_int),
+        "mgp_hclust": ([C.c_int, vp, i64, i64, vp, vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -710,6 +713,55 @@ def position_depth_hist_rows(depth: np.ndarray, shift: int, prefix=None, cells=N
 def position_depth_next_rows(depth: np.ndarray, v, cells=None, device: int = 0) -> dict:
     """mgp_position_depth_next_rows: Engine.position_depth_next on caller-supplied u32 depths."""
     return _coverage_rows_calls(None, None, depth, device)[3](v, cells)
+
+
+CLUSTER_MAX_ITEMS = 1 << 16  # items of one mgp_pair_dist / mgp_hclust* call (8 n^2 bytes of distances)
+
+
+def _cluster_x(x) -> np.ndarray:
+    x = np.ascontiguousarray(x, np.float64)
+    if x.ndim != 2:
+        raise InvalidInputError("x is [n_feat, n_items]")
+    return x
+
+
+def _cluster_outputs(n: int):
+    return np.zeros((max(n - 1, 0), 2), np.int32), np.zeros(max(n - 1, 0), np.float64), np.zeros(n, np.int32)
+
+
+def cluster_pair_dist(x, device: int = 0) -> np.ndarray:
+    """mgp_pair_dist: [n, n] Euclidean distances of the columns of x [n_feat, n_items] (fp64,
+    every value finite; at most CLUSTER_MAX_ITEMS items)."""
+    x = _cluster_x(x)
+    nf, n = x.shape
+    out = np.zeros((n, n), np.float64) if n <= CLUSTER_MAX_ITEMS else None  # (above: refused before any use)
+    _ck(load_library().mgp_pair_dist(int(device), _ptr(x), n, nf, _ptr(out)), "mgp_pair_dist")
+    return out
+
+
+def cluster_hclust_dist(dist, device: int = 0):
+    """mgp_hclust_dist: (merge [n - 1, 2], height [n - 1], order [n]) of complete linkage on
+    the symmetric, finite, non-negative matrix dist [n, n], in R's hclust conventions."""
+    dist = np.ascontiguousarray(dist, np.float64)
+    if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+        raise InvalidInputError("dist is [n, n]")
+    n = dist.shape[0]
+    merge, height, order = _cluster_outputs(min(n, CLUSTER_MAX_ITEMS))
+    _ck(load_library().mgp_hclust_dist(int(device), _ptr(dist), n, _ptr(merge), _ptr(height), _ptr(order)),
+        "mgp_hclust_dist")
+    return merge, height, order
+
+
+def cluster_hclust(x, device: int = 0, want_dist: bool = False):
+    """mgp_hclust: the distances and the linkage of the columns of x [n_feat, n_items] in one
+    call; (merge, height, order, dist or None). The matrix stays on the device unless asked for."""
+    x = _cluster_x(x)
+    nf, n = x.shape
+    merge, height, order = _cluster_outputs(min(n, CLUSTER_MAX_ITEMS))
+    dist = np.zeros((n, n), np.float64) if want_dist and n <= CLUSTER_MAX_ITEMS else None
+    _ck(load_library().mgp_hclust(int(device), _ptr(x), n, nf, _ptr(merge), _ptr(height), _ptr(order), _ptr(dist)),
+        "mgp_hclust")
+    return merge, height, order, dist
 
 
 class Engine:

@@ -99,6 +99,8 @@ class MtDNAPipeline:
         cell_min_mean_coverage: float = 0.0,
         cell_min_coverage_breadth: float = 0.0,
         recompute_reference: bool = False,
+        cluster: bool = False,
+        clones: int | None = None,
     ):
         self.bam_path = Path(bam_path)
         # streamed ingest (default; MGP_STREAM=0 decodes the whole chrM set first)
@@ -128,6 +130,16 @@ class MtDNAPipeline:
                                      recompute_reference=bool(recompute_reference))
         self.coverage_on = (self.coverage_stats or bool(recompute_reference) or cell_min_mean_coverage > 0
                             or cell_min_coverage_breadth > 0)
+        # clustering of the heteroplasmy matrix (off unless asked for): the trees, the heatmap
+        # orders and, with clones = K, the clone labels, in variants/
+        self.cluster = bool(cluster)
+        self.clones = None if clones is None else int(clones)
+        if self.cluster and not self.call_variants:
+            raise InvalidInputError("cluster needs call_variants (--cluster requires --variants)")
+        if self.clones is not None and not self.cluster:
+            raise InvalidInputError("clones needs cluster (--clones requires --cluster)")
+        if self.clones is not None and self.clones < 1:
+            raise InvalidInputError(f"clones must be at least 1, got {self.clones}")
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -179,6 +191,8 @@ class MtDNAPipeline:
             processor.enable_variants(**self.variant_options)
         if self.coverage_on:
             processor.enable_coverage(**self.coverage_options)
+        if self.cluster:
+            processor.enable_clustering(self.clones)
         if self.stream:
             # one pass: batches decoded on a producer thread, each pushed to the device as
             # it is ready, the windows piled as their reads arrive (readers.py:84-93)
@@ -264,14 +278,26 @@ class MtDNAPipeline:
             except Exception as e:
                 logger.warning("Failed to generate HTML report: %s", e)
         t4 = time.time()
+        if self.cluster and getattr(res, "variants", None) is not None:
+            # last, so that a population above the clustering's bound raises with every other
+            # output written; the run's engine contexts closed long ago
+            from .analysis.clustering import write_cluster_outputs
+
+            kept = getattr(res, "variant_cells", None)
+            names = self.barcode_list if kept is None else [self.barcode_list[int(i)] for i in kept]
+            clusters = processor.cluster_result(res)
+            write_cluster_outputs(clusters, names, res.variants, self.output_dir)
+            if clusters.cells is not None:
+                logger.info("Clustered %d cells and %d variants", clusters.cells.n, clusters.variants.n)
+        t5 = time.time()  # (the clustering's seconds are last_timing["cluster"])
         # streamed: bam_ingest ends with the last decoded batch and `engine` is only what the
         # device still did after it (the rest ran under the decode)
         self.timings = {"bam_ingest": t1 - t0, "engine": t2 - t1, "write": t3 - t2, "report": t4 - t3,
-                        "total": t4 - t0, "engine_setup": ta - t1, "engine_run_soa": tb - ta,
+                        "total": t5 - t0, "engine_setup": ta - t1, "engine_run_soa": tb - ta,
                         "engine_free_inputs": t2 - tb, "streamed": bool(self.stream),
                         **processor.last_timing}
         logger.info("Pipeline complete")
-        logger.info("Elapsed time: %.1fs (ingest %.1fs, engine %.1fs, write %.1fs)", t4 - t0, t1 - t0, t2 - t1,
+        logger.info("Elapsed time: %.1fs (ingest %.1fs, engine %.1fs, write %.1fs)", t5 - t0, t1 - t0, t2 - t1,
                     t3 - t2)
         return {
             "cells_processed": n_cells_input,
@@ -318,6 +344,8 @@ def run_pipeline(
     cell_min_mean_coverage: float = 0.0,
     cell_min_coverage_breadth: float = 0.0,
     recompute_reference: bool = False,
+    cluster: bool = False,
+    clones: int | None = None,
 ) -> dict[str, Any]:
     """pipeline.py:183-269. ``min_distance_from_end`` is accepted and, as in the
     reference, not passed on (the engine uses 5). ``call_variants``
@@ -326,7 +354,11 @@ def run_pipeline(
     half of that R workflow: cell, position, strand and transposition tables);
     ``cell_min_mean_coverage`` / ``cell_min_coverage_breadth`` filter the cells those position
     tables and the variants are made of, ``recompute_reference`` gives the variants the kept
-    cells' own reference alleles (and writes coverage/reference_alleles.tsv)."""
+    cells' own reference alleles (and writes coverage/reference_alleles.tsv). ``cluster`` (needs
+    ``call_variants``) clusters the cells and the variants of the heteroplasmy matrix on the
+    device (the vignette's pheatmap step: Euclidean distances, complete linkage) and writes the
+    trees and the heatmap orders to variants/; ``clones`` = K (needs ``cluster``) also writes the
+    cell tree cut into K clones."""
     barcode_metadata = None
     if barcode_file is None:
         from .file_io.barcode_extraction import extract_barcodes_from_bam
@@ -366,6 +398,6 @@ def run_pipeline(
         variant_stabilize=variant_stabilize, variant_low_coverage=variant_low_coverage,
         variant_min_coverage=variant_min_coverage, coverage_stats=coverage_stats,
         cell_min_mean_coverage=cell_min_mean_coverage, cell_min_coverage_breadth=cell_min_coverage_breadth,
-        recompute_reference=recompute_reference,
+        recompute_reference=recompute_reference, cluster=cluster, clones=clones,
     )
     return pipeline.run()

@@ -25,6 +25,7 @@ from queue import Queue
 import numpy as np
 
 from ..engine import TXT_FILES, Engine, EngineResult, PinnedBuffer, Rows16
+from ..exceptions import InvalidInputError
 from ..synth import ReadSoA, pack_reads
 from .pileup import result_dict, simple_reads_to_dicts
 
@@ -115,6 +116,7 @@ class CellProcessor:
         self.h5_out = None
         self.variants_opt: dict | None = None
         self.coverage_opt: dict | None = None
+        self.cluster_opt: dict | None = None
         self._t_cov = self._t_var = 0.0
 
     # txt output on the device ----------------------------------------------
@@ -167,6 +169,33 @@ class CellProcessor:
         vr = run_variants(parts, ref, cells=pop, **self.variants_opt)
         res.variants, res.allele_freq, res.variant_seconds = vr.table, vr.allele_freq, vr.seconds
         return time.perf_counter() - t0
+
+    def enable_clustering(self, clones: int | None = None):
+        """Cluster the cells and the variants of the run's heteroplasmy matrix (mgp_hclust;
+        analysis/clustering.py) when cluster_result is called; needs enable_variants. `clones`
+        = K also cuts the cell tree into K clones."""
+        if self.variants_opt is None:
+            raise InvalidInputError("clustering needs the variants (enable_variants first)")
+        if clones is not None and int(clones) < 1:
+            raise InvalidInputError(f"clones must be at least 1, got {clones}")
+        self.cluster_opt = dict(clones=None if clones is None else int(clones))
+
+    def cluster_result(self, res: EngineResult):
+        """The clustering of a finished run's matrix (res.allele_freq, the host-merged matrix of
+        every part): one call per side on the first device, after the run's engine contexts have
+        closed, so its distance matrix never competes with the run's buffers. Sets res.clusters
+        and last_timing["cluster"]; returns the ClusterResult (None when not enabled)."""
+        if self.cluster_opt is None:
+            return None
+        from ..analysis.clustering import cluster_heteroplasmy
+
+        t0 = time.perf_counter()
+        try:
+            res.clusters = cluster_heteroplasmy(getattr(res, "allele_freq", None), table=getattr(res, "variants", None),
+                                                clones=self.cluster_opt["clones"], device=self.devices[0])
+        finally:
+            self.last_timing["cluster"] = time.perf_counter() - t0
+        return res.clusters
 
     @staticmethod
     def _population(res: EngineResult) -> np.ndarray:
