@@ -67,7 +67,9 @@ extern "C" {
                                  mgp_position_depth_hist_*, mgp_position_depth_next_*
                                  (coverage QC on the device),
                                  mgp_pair_dist, mgp_hclust_dist, mgp_hclust (clustering by
-                                 heteroplasmy on the device) */
+                                 heteroplasmy on the device),
+                                 mgp_knn, mgp_snn (the cells' kNN and SNN graphs by heteroplasmy
+                                 on the device) */
 
 /* ---- return codes (0 = success) ------------------------------------------ */
 #define MGP_OK               0
@@ -738,6 +740,41 @@ int  mgp_hclust_dist(int device, const double *dist, int64_t n_items, int32_t *m
 /* Both; the matrix stays on the device unless out_dist [n][n] is given (it may be NULL). */
 int  mgp_hclust(int device, const double *x, int64_t n_items, int64_t n_feat, int32_t *merge, double *height,
                 int32_t *order, double *out_dist);
+/* The cells' neighbour graphs by heteroplasmy on the device (added under ABI 7): the step of
+ * the vignette's "Integration with Seurat/Signac", Signac's FindClonotypes -> FindNeighbors, a
+ * k-nearest-neighbour graph of the cells over the variants and Seurat's ComputeSNN on it (the
+ * input of FindClusters, igraph or leidenalg; community detection itself is not done here). No
+ * engine context, buffers of the call's own, all freed on return (MGP_E_OOM leaves nothing
+ * allocated). Items are the columns of x [n_feat][n_items] as for mgp_pair_dist, every value
+ * finite (MGP_E_INVALID otherwise), and the distance of a pair is the number mgp_pair_dist
+ * returns for it, bit for bit; the n x n matrix is never stored.
+ * kNN: row i of out_idx (0-based) and out_dist holds the k items j != i smallest under the
+ * strict total order (distance, then j), in that order: row i of mgp_pair_dist's matrix sorted
+ * by (value, index), i dropped, the first k. The result depends on the input alone (not on
+ * the tiling or on MGP_KNN_SPLITS, the number of splits S of the candidate range; 0 or unset:
+ * automatic).
+ * Bounds, checked before any allocation or device call (MGP_E_INVALID): 1 <= k <= 64,
+ * k <= n_items - 1, n_items <= 2^20, n_feat <= 2^24. n_items == 0: nothing is launched.
+ * Device memory: 8 n n_feat + 12 S n k (the splits' lists) + 12 n k bytes. */
+int  mgp_knn(int device, const double *x, int64_t n_items, int64_t n_feat, int32_t k,
+             int32_t *out_idx /* [n][k] */, double *out_dist /* [n][k] */);
+/* SNN by Seurat's ComputeSNN from a kNN table knn_idx [n][k] (checked on the device: every entry
+ * in [0, n), not its own row, distinct within the row; MGP_E_INVALID otherwise).
+ * S_i = {i} + knn[i] (K = k + 1 members, Seurat's k.param), shared(i, j) = |S_i & S_j|, the
+ * Jaccard weight shared / (2K - shared). The device works in integers: it returns the triples
+ * (i, j, shared) with i < j and shared >= min_shared (1 <= min_shared <= k + 1: the caller turns
+ * Seurat's `prune` into the smallest count whose weight passes), in no particular order (the
+ * set is unique); the weight is the caller's one division and the diagonal (weight 1) implicit.
+ * *n_edges is always set to the true count (0 when the arguments are refused). When it
+ * exceeds `capacity`, no triple is written and MGP_E_INVALID returned with the count in the
+ * message: call with capacity 0 (the arrays may then be NULL), then with the count. More than
+ * 2^30 edges are refused: a block of identical items, such as the all-zero columns of a sparse
+ * matrix, gives a dense block and the output is then quadratic in its size.
+ * Device memory: 4 n k + 8 n K (the sorted sets and the reverse lists as CSR) + 28 n + 12 per
+ * edge. */
+int  mgp_snn(int device, const int32_t *knn_idx /* [n][k] */, int64_t n_items, int32_t k, int32_t min_shared,
+             int64_t capacity, int64_t *n_edges, int32_t *out_i, int32_t *out_j,
+             int32_t *out_shared /* [capacity] each, may be NULL when capacity == 0 */);
 /* Position windows of the pileup (the `wide` flags' second dimension). */
 int  mgp_windows(mgp_ctx *ctx, int32_t *n_windows, int32_t *window_width);
 /* Wait until the H2D copies of every batch pushed so far have completed: the caller may

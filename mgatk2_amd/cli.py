@@ -7,7 +7,8 @@ Added: ``--device`` (HIP device ordinal for the engine), ``--variants`` with its
 and ``--coverage-stats`` / ``--cell-min-mean-coverage`` / ``--cell-min-coverage-breadth`` /
 ``--recompute-reference`` (coverage QC and the cell filter from the device's rows, coverage/),
 and ``--cluster`` / ``--clones K`` (the heteroplasmy matrix's cells and variants clustered on
-the device, the trees and heatmap orders in variants/).
+the device, the trees and heatmap orders in variants/), and ``--neighbors K`` / ``--snn-prune P``
+(the cells' kNN and SNN graphs by heteroplasmy on the device, in variants/).
 Not carried over: ``hardmask-fasta`` (FASTA masking utility, outside the hot path).
 """
 
@@ -64,6 +65,13 @@ def _variant_options(f):
                           "variants/{cell,variant}_{hclust,order}.tsv; needs --variants"),
         click.option("--clones", default=None, type=click.IntRange(min=1), metavar="K",
                      help="Cut the cell tree into K clones (variants/cell_clones.tsv); needs --cluster"),
+        click.option("--neighbors", default=None, type=click.IntRange(min=2, max=65), metavar="K",
+                     help="kNN and SNN graphs of the cells by heteroplasmy on the device, K as Seurat's k.param "
+                          "(the cell and its K - 1 nearest others): variants/cell_knn.tsv, cell_snn.mtx, "
+                          "cell_snn_barcodes.tsv; needs --variants"),
+        click.option("--snn-prune", default=None, type=click.FloatRange(min=0.0, max=1.0), metavar="P",
+                     help="Drop SNN edges of Jaccard weight below P (Seurat's prune.SNN)  [default: 1/15]; "
+                          "needs --neighbors"),
     ]
     for o in reversed(opts):
         f = o(f)
@@ -72,11 +80,18 @@ def _variant_options(f):
 
 def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
                   variant_low_coverage, variant_min_coverage, coverage_stats=False, cell_min_mean_coverage=0.0,
-                  cell_min_coverage_breadth=0.0, recompute_reference=False, cluster=False, clones=None) -> dict:
+                  cell_min_coverage_breadth=0.0, recompute_reference=False, cluster=False, clones=None, neighbors=None,
+                  snn_prune=None) -> dict:
     """The options run_pipeline gets beyond the reference's, each only when asked for: the
     variant options with --variants; the four coverage options with --coverage-stats,
     otherwise the filter thresholds and --recompute-reference that were given; --cluster and
-    --clones when given (--cluster needs --variants, --clones needs --cluster: a usage error)."""
+    --clones when given (--cluster needs --variants, --clones needs --cluster: a usage error);
+    --neighbors and --snn-prune when given (--neighbors needs --variants, --snn-prune needs
+    --neighbors: a usage error)."""
+    if neighbors is not None and not call_variants:
+        raise click.UsageError("--neighbors requires --variants")
+    if snn_prune is not None and neighbors is None:
+        raise click.UsageError("--snn-prune requires --neighbors")
     if cluster and not call_variants:
         raise click.UsageError("--cluster requires --variants")
     if clones is not None and not cluster:
@@ -100,6 +115,10 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
         out.update(cluster=True)
         if clones is not None:
             out.update(clones=int(clones))
+    if neighbors is not None:
+        out.update(neighbors=int(neighbors))
+        if snn_prune is not None:
+            out.update(snn_prune=float(snn_prune))
     return out
 
 
@@ -310,6 +329,9 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
                         variant_args.get("recompute_reference", False))
         if variant_args and variant_args.get("cluster"):
             logger.info("  Clustering:             complete linkage, clones %s", variant_args.get("clones"))
+        if variant_args and variant_args.get("neighbors") is not None:
+            logger.info("  Neighbour graph:        k.param %s, SNN prune %s", variant_args["neighbors"],
+                        variant_args.get("snn_prune", "1/15"))
         if dry_run:
             return 0
         if report_title is None:

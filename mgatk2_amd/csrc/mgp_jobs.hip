@@ -4,7 +4,8 @@
 // (mgp_qc.hip). Each job has two forms: *_run on a context's last run, whose rows it gets
 // through run_rows (mgp_jobs.h: the context itself is opaque here), and the detached
 // *_rows form on u32 rows of the caller's (on_rows). The clustering of the heteroplasmy
-// matrix (mgp_cluster.hip) reads no rows and needs no context: mgp_pair_dist / mgp_hclust*.
+// matrix (mgp_cluster.hip) reads no rows and needs no context: mgp_pair_dist / mgp_hclust*;
+// nor do the cells' neighbour graphs (mgp_graph.hip): mgp_knn / mgp_snn.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 
 #include "../../include/mgpileup.h"
 #include "mgp_cluster.h"
+#include "mgp_graph.h"
 #include "mgp_host.h"
 #include "mgp_jobs.h"
 #include "mgp_qc.h"
@@ -52,6 +54,12 @@ struct QcState {
 // mgp_pair_dist / mgp_hclust*: the clustering's buffers (mgp_cluster.hip), a call's own
 struct ClusterState {
     DevBuf x, dist, bad, nn, dnn, act, list, si, sj, sh;
+};
+
+// mgp_knn / mgp_snn: the neighbour graphs' buffers (mgp_graph.hip), a call's own
+struct GraphState {
+    DevBuf x, bad, part_dist, part_idx, out_dist, out_idx;                 // mgp_knn
+    DevBuf idx, sets, deg, off, cur, rev, cnt, eoff, ei, ej, es;  // mgp_snn
 };
 
 struct RowJobs {
@@ -104,16 +112,16 @@ static int on_rows(int device, const char* who, int need, const HostRows& h, Job
     return rc;
 }
 
-// The clustering calls: job(state, stream) on `device` with a stream and a ClusterState of
+// The clustering and graph calls: job(state, stream) on `device` with a stream and a State of
 // the call's own, freed once that stream is idle.
-template <class Job>
+template <class State = ClusterState, class Job>
 static int cl_call(int device, Job&& job) {
     HIP_TRY(hipSetDevice(device));
     hipStream_t s = nullptr;
     HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     int rc;
     {
-        ClusterState st;
+        State st;
         rc = job(st, s);
         (void)hipStreamSynchronize(s);
     }
@@ -935,6 +943,148 @@ int mgp_hclust(int device, const double* x, int64_t n_items, int64_t n_feat, int
         if (out_dist)  // (before the linkage overwrites the matrix)
             HIP_TRY(hipMemcpyAsync(out_dist, st.dist.p, (size_t)n_items * (size_t)n_items * 8, hipMemcpyDeviceToHost, s));
         return cl_link(st, s, who, n_items, merge, height, order);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// mgp_knn / mgp_snn: the cells' k-nearest-neighbour graph over the heteroplasmy matrix's
+// columns and Seurat's shared-nearest-neighbour graph of it (Signac's FindClonotypes ->
+// FindNeighbors, the vignette's "Integration with Seurat/Signac"). No engine context, as the
+// clustering: a call has its own stream and buffers, all freed when it returns.
+// ---------------------------------------------------------------------------
+// the checks before any device call that the two share: the sizes, then k against them
+static int gr_args(const char* who, int64_t n, int64_t nf, int32_t k) {
+    if (n < 0 || nf < 0) return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    if (n > graph::kMaxItems) return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^20 items in one call");
+    if (nf > graph::kMaxFeat) return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^24 features in one call");
+    if (k < 1 || k > graph::kMaxK)
+        return set_err(MGP_E_INVALID, std::string(who) + ": k must be in 1..64 (a row's list is one entry per lane)");
+    if (n > 0 && k > n - 1)
+        return set_err(MGP_E_INVALID, std::string(who) + ": k must be at most n_items - 1 (an item is not its own "
+                                                         "neighbour)");
+    return MGP_OK;
+}
+
+static int gr_bad(GraphState& st, hipStream_t s, uint32_t* bad) {
+    HIP_TRY(hipMemcpyAsync(bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MGP_OK;
+}
+
+int mgp_knn(int device, const double* x, int64_t n_items, int64_t n_feat, int32_t k, int32_t* out_idx,
+            double* out_dist) {
+    const char* who = "mgp_knn";
+    MGP_TRY(gr_args(who, n_items, n_feat, k));
+    if (n_items > 0 && (!out_idx || !out_dist || (n_feat > 0 && !x)))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    if (n_items == 0) return MGP_OK;
+    const char* env = std::getenv("MGP_KNN_SPLITS");  // the candidate splits (0 or unset: automatic)
+    const int splits = graph::knn_splits((int)n_items, env ? std::atoi(env) : 0);
+    return cl_call<GraphState>(device, [&](GraphState& st, hipStream_t s) {
+        const size_t n = (size_t)n_items, nk = n * (size_t)k;
+        MGP_TRY(st.x.ensure(std::max<size_t>(n * (size_t)n_feat * 8, 8)));
+        MGP_TRY(st.bad.ensure(4));
+        MGP_TRY(st.part_dist.ensure((size_t)splits * nk * 8));
+        MGP_TRY(st.part_idx.ensure((size_t)splits * nk * 4));
+        MGP_TRY(st.out_dist.ensure(nk * 8));
+        MGP_TRY(st.out_idx.ensure(nk * 4));
+        if (n_feat) HIP_TRY(hipMemcpyAsync(st.x.p, x, n * (size_t)n_feat * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(st.bad.p, 0, 4, s));
+        VarProf prof(s);
+        if (graph::knn(st.x.as<double>(), (int)n_items, (int)n_feat, k, splits, st.part_dist.as<double>(),
+                       st.part_idx.as<int32_t>(), st.out_dist.as<double>(), st.out_idx.as<int32_t>(),
+                       st.bad.as<uint32_t>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+        prof.stop();
+        uint32_t bad = 0;
+        MGP_TRY(gr_bad(st, s, &bad));
+        prof.report(who, (std::string("items x features, kNN, splits ") + std::to_string(splits)).c_str(), n_items,
+                    n_feat);
+        if (bad) return set_err(MGP_E_INVALID, std::string(who) + ": a value of x is not finite");
+        HIP_TRY(hipMemcpyAsync(out_dist, st.out_dist.p, nk * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_idx, st.out_idx.p, nk * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return (int)MGP_OK;
+    });
+}
+
+int mgp_snn(int device, const int32_t* knn_idx, int64_t n_items, int32_t k, int32_t min_shared, int64_t capacity,
+            int64_t* n_edges, int32_t* out_i, int32_t* out_j, int32_t* out_shared) {
+    const char* who = "mgp_snn";
+    if (n_edges) *n_edges = 0;
+    MGP_TRY(gr_args(who, n_items, 0, k));
+    if (min_shared < 1 || min_shared > k + 1)
+        return set_err(MGP_E_INVALID, std::string(who) + ": min_shared must be in 1..k + 1");
+    if (!n_edges || capacity < 0 || (n_items > 0 && !knn_idx) || (capacity > 0 && (!out_i || !out_j || !out_shared)))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    if (n_items == 0) return MGP_OK;
+    return cl_call<GraphState>(device, [&](GraphState& st, hipStream_t s) {
+        const int n = (int)n_items;
+        const size_t un = (size_t)n_items, nk = un * (size_t)k, nkk = un * (size_t)(k + 1);
+        MGP_TRY(st.idx.ensure(nk * 4));
+        MGP_TRY(st.bad.ensure(4));
+        HIP_TRY(hipMemcpyAsync(st.idx.p, knn_idx, nk * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(st.bad.p, 0, 4, s));
+        VarProf check(s);
+        if (graph::knn_check(st.idx.as<int32_t>(), n, k, st.bad.as<uint32_t>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": check kernel launch failed");
+        check.stop();
+        uint32_t bad = 0;
+        MGP_TRY(gr_bad(st, s, &bad));
+        check.report(who, "items x k, table check", n_items, k);
+        if (bad)
+            return set_err(MGP_E_INVALID, std::string(who) + ": the kNN table has an entry out of range, a row that "
+                                                             "names itself or a repeated entry");
+        MGP_TRY(st.sets.ensure(nkk * 4));
+        MGP_TRY(st.deg.ensure(un * 4));
+        MGP_TRY(st.off.ensure((un + 1) * 8));
+        MGP_TRY(st.cur.ensure(un * 4));
+        MGP_TRY(st.rev.ensure(nkk * 4));
+        MGP_TRY(st.cnt.ensure(un * 4));
+        MGP_TRY(st.eoff.ensure((un + 1) * 8));
+        const int32_t* sets = st.sets.as<int32_t>();
+        const int64_t* off = st.off.as<int64_t>();
+        VarProf csr(s);
+        if (graph::snn_sets(st.idx.as<int32_t>(), n, k, st.sets.as<int32_t>(), st.deg.as<int32_t>(), s) != 0 ||
+            graph::scan(st.deg.as<int32_t>(), n, st.off.as<int64_t>(), s) != 0 ||
+            graph::snn_reverse(sets, n, k, off, st.cur.as<int32_t>(), st.rev.as<int32_t>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": CSR kernel launch failed");
+        csr.stop();
+        VarProf count(s);
+        if (graph::snn_edges(sets, n, k, off, st.rev.as<int32_t>(), min_shared, st.cnt.as<int32_t>(), nullptr, nullptr,
+                             nullptr, nullptr, s) != 0 ||
+            graph::scan(st.cnt.as<int32_t>(), n, st.eoff.as<int64_t>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": count kernel launch failed");
+        count.stop();
+        int64_t total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, st.eoff.as<int64_t>() + un, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        csr.report(who, "items x k, sorted sets and reverse lists", n_items, k);
+        count.report(who, "items, edges, count pass", n_items, total);
+        *n_edges = total;
+        if (total > graph::kMaxEdges)
+            return set_err(MGP_E_INVALID, std::string(who) + ": " + std::to_string(total) + " edges, more than 2^30 in "
+                           "one call (a block of identical items gives a dense block: the output is then quadratic "
+                           "in its size)");
+        if (total > capacity)
+            return set_err(MGP_E_INVALID, std::string(who) + ": " + std::to_string(total) + " edges, capacity " +
+                                              std::to_string(capacity));
+        if (total == 0) return (int)MGP_OK;
+        const size_t ne = (size_t)total;
+        MGP_TRY(st.ei.ensure(ne * 4));
+        MGP_TRY(st.ej.ensure(ne * 4));
+        MGP_TRY(st.es.ensure(ne * 4));
+        VarProf fill(s);
+        if (graph::snn_edges(sets, n, k, off, st.rev.as<int32_t>(), min_shared, nullptr, st.eoff.as<int64_t>(),
+                             st.ei.as<int32_t>(), st.ej.as<int32_t>(), st.es.as<int32_t>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": fill kernel launch failed");
+        fill.stop();
+        HIP_TRY(hipMemcpyAsync(out_i, st.ei.p, ne * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_j, st.ej.p, ne * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_shared, st.es.p, ne * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        fill.report(who, "items, edges, fill pass", n_items, total);
+        return (int)MGP_OK;
     });
 }
 

@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "mgp_cell_coverage_run", "mgp_position_coverage_run", "mgp_position_depth_hist_run",
     "mgp_position_depth_next_run", "mgp_cell_coverage_rows", "mgp_position_coverage_rows",
     "mgp_position_depth_hist_rows", "mgp_position_depth_next_rows", "mgp_pair_dist", "mgp_hclust_dist", "mgp_hclust",
+    "mgp_knn", "mgp_snn",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -313,6 +314,8 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_pair_dist": ([C.c_int, vp, i64, i64, vp], C.c_int),
         "mgp_hclust_dist": ([C.c_int, vp, i64, vp, vp, vp], C.c_int),
         "mgp_hclust": ([C.c_int, vp, i64, i64, vp, vp, vp, vp], C.c_int),
+        "mgp_knn": ([C.c_int, vp, i64, i64, i32, vp, vp], C.c_int),
+        "mgp_snn": ([C.c_int, vp, i64, i32, i32, i64, C.POINTER(i64), vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -762,6 +765,45 @@ def cluster_hclust(x, device: int = 0, want_dist: bool = False):
     _ck(load_library().mgp_hclust(int(device), _ptr(x), n, nf, _ptr(merge), _ptr(height), _ptr(order), _ptr(dist)),
         "mgp_hclust")
     return merge, height, order, dist
+
+
+GRAPH_MAX_ITEMS = 1 << 20  # items of one mgp_knn / mgp_snn call
+GRAPH_MAX_K = 64           # neighbours per item (Seurat's k.param - 1)
+
+
+def graph_knn(x, k: int, device: int = 0):
+    """mgp_knn: (idx [n, k] int32, dist [n, k]) of the columns of x [n_feat, n_items]: per item
+    the k others smallest under (distance, index), in that order; the distances are
+    mgp_pair_dist's. 1 <= k <= min(GRAPH_MAX_K, n - 1)."""
+    x = _cluster_x(x)
+    nf, n = x.shape
+    ok = n <= GRAPH_MAX_ITEMS and 1 <= int(k) <= GRAPH_MAX_K  # (otherwise refused before any use)
+    idx = np.zeros((n, int(k)), np.int32) if ok else None
+    dist = np.zeros((n, int(k)), np.float64) if ok else None
+    _ck(load_library().mgp_knn(int(device), _ptr(x), n, nf, int(k), _ptr(idx), _ptr(dist)), "mgp_knn")
+    return idx, dist
+
+
+def graph_snn(idx, min_shared: int, device: int = 0):
+    """mgp_snn: (i, j, shared) int32 arrays of the pairs i < j whose sets S = {row} + idx[row]
+    share at least min_shared members, from the kNN table idx [n, k]; sorted by (i, j) here (the
+    device's order is free). Two calls: the count, then the triples."""
+    idx = np.ascontiguousarray(idx, np.int32)
+    if idx.ndim != 2:
+        raise InvalidInputError("idx is [n_items, k]")
+    n, k = idx.shape
+    lib = load_library()
+    count = C.c_int64(0)
+    rc = lib.mgp_snn(int(device), _ptr(idx), n, k, int(min_shared), 0, C.byref(count), None, None, None)
+    if rc != MGP_OK and not (rc == MGP_E_INVALID and 0 < count.value <= 1 << 30):
+        _raise(rc, "mgp_snn")
+    ne = int(count.value)
+    out = [np.zeros(ne, np.int32) for _ in range(3)]
+    if ne:
+        _ck(lib.mgp_snn(int(device), _ptr(idx), n, k, int(min_shared), ne, C.byref(count), *map(_ptr, out)), "mgp_snn")
+        order = np.lexsort((out[1], out[0]))
+        out = [a[order] for a in out]
+    return tuple(out)
 
 
 class Engine:

@@ -101,6 +101,8 @@ class MtDNAPipeline:
         recompute_reference: bool = False,
         cluster: bool = False,
         clones: int | None = None,
+        neighbors: int | None = None,
+        snn_prune: float = 1.0 / 15.0,
     ):
         self.bam_path = Path(bam_path)
         # streamed ingest (default; MGP_STREAM=0 decodes the whole chrM set first)
@@ -140,6 +142,15 @@ class MtDNAPipeline:
             raise InvalidInputError("clones needs cluster (--clones requires --cluster)")
         if self.clones is not None and self.clones < 1:
             raise InvalidInputError(f"clones must be at least 1, got {self.clones}")
+        # the cells' kNN and SNN graphs of the heteroplasmy matrix (off unless asked for), in variants/
+        self.neighbors = None if neighbors is None else int(neighbors)
+        self.snn_prune = float(snn_prune)
+        if self.neighbors is not None and not self.call_variants:
+            raise InvalidInputError("neighbors needs call_variants (--neighbors requires --variants)")
+        if self.neighbors is not None and not 2 <= self.neighbors <= 65:
+            raise InvalidInputError(f"neighbors must be in 2..65, got {self.neighbors}")
+        if not 0.0 <= self.snn_prune <= 1.0:
+            raise InvalidInputError(f"snn_prune must be in [0, 1], got {self.snn_prune}")
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -193,6 +204,8 @@ class MtDNAPipeline:
             processor.enable_coverage(**self.coverage_options)
         if self.cluster:
             processor.enable_clustering(self.clones)
+        if self.neighbors is not None:
+            processor.enable_neighbors(self.neighbors, self.snn_prune)
         if self.stream:
             # one pass: batches decoded on a producer thread, each pushed to the device as
             # it is ready, the windows piled as their reads arrive (readers.py:84-93)
@@ -289,7 +302,18 @@ class MtDNAPipeline:
             write_cluster_outputs(clusters, names, res.variants, self.output_dir)
             if clusters.cells is not None:
                 logger.info("Clustered %d cells and %d variants", clusters.cells.n, clusters.variants.n)
-        t5 = time.time()  # (the clustering's seconds are last_timing["cluster"])
+        if self.neighbors is not None and getattr(res, "variants", None) is not None:
+            # after the clustering, for the same reason
+            from .analysis.neighbors import write_neighbor_outputs
+
+            kept = getattr(res, "variant_cells", None)
+            names = self.barcode_list if kept is None else [self.barcode_list[int(i)] for i in kept]
+            graph = processor.neighbor_result(res)
+            write_neighbor_outputs(graph, names, self.output_dir)
+            if graph.idx is not None:
+                logger.info("Neighbour graph: %d cells, k.param %d, %d SNN edges", graph.n, graph.k_param,
+                            int(graph.i.size))
+        t5 = time.time()  # (the clustering's seconds are last_timing["cluster"], the graphs' ["neighbors"])
         # streamed: bam_ingest ends with the last decoded batch and `engine` is only what the
         # device still did after it (the rest ran under the decode)
         self.timings = {"bam_ingest": t1 - t0, "engine": t2 - t1, "write": t3 - t2, "report": t4 - t3,
@@ -346,6 +370,8 @@ def run_pipeline(
     recompute_reference: bool = False,
     cluster: bool = False,
     clones: int | None = None,
+    neighbors: int | None = None,
+    snn_prune: float = 1.0 / 15.0,
 ) -> dict[str, Any]:
     """pipeline.py:183-269. ``min_distance_from_end`` is accepted and, as in the
     reference, not passed on (the engine uses 5). ``call_variants``
@@ -358,7 +384,10 @@ def run_pipeline(
     ``call_variants``) clusters the cells and the variants of the heteroplasmy matrix on the
     device (the vignette's pheatmap step: Euclidean distances, complete linkage) and writes the
     trees and the heatmap orders to variants/; ``clones`` = K (needs ``cluster``) also writes the
-    cell tree cut into K clones."""
+    cell tree cut into K clones. ``neighbors`` = K (needs ``call_variants``; Seurat's k.param, 2..65)
+    builds the cells' kNN graph over the variants and its SNN graph (Jaccard weights, ``snn_prune``
+    as Seurat's prune.SNN) on the device and writes variants/cell_knn.tsv, cell_snn.mtx and
+    cell_snn_barcodes.tsv."""
     barcode_metadata = None
     if barcode_file is None:
         from .file_io.barcode_extraction import extract_barcodes_from_bam
@@ -399,5 +428,6 @@ def run_pipeline(
         variant_min_coverage=variant_min_coverage, coverage_stats=coverage_stats,
         cell_min_mean_coverage=cell_min_mean_coverage, cell_min_coverage_breadth=cell_min_coverage_breadth,
         recompute_reference=recompute_reference, cluster=cluster, clones=clones,
+        neighbors=neighbors, snn_prune=snn_prune,
     )
     return pipeline.run()

@@ -117,6 +117,7 @@ class CellProcessor:
         self.variants_opt: dict | None = None
         self.coverage_opt: dict | None = None
         self.cluster_opt: dict | None = None
+        self.neighbors_opt: dict | None = None
         self._t_cov = self._t_var = 0.0
 
     # txt output on the device ----------------------------------------------
@@ -196,6 +197,37 @@ class CellProcessor:
         finally:
             self.last_timing["cluster"] = time.perf_counter() - t0
         return res.clusters
+
+    def enable_neighbors(self, neighbors: int = 20, prune: float = 1.0 / 15.0):
+        """Build the cells' kNN and SNN graphs of the run's heteroplasmy matrix (mgp_knn / mgp_snn;
+        analysis/neighbors.py) when neighbor_result is called; needs enable_variants. `neighbors`
+        = K is Seurat's k.param (the cell and its K - 1 nearest others), `prune` its prune.SNN."""
+        from ..analysis.neighbors import GRAPH_MAX_K
+
+        if self.variants_opt is None:
+            raise InvalidInputError("the neighbour graph needs the variants (enable_variants first)")
+        if not 2 <= int(neighbors) <= GRAPH_MAX_K + 1:
+            raise InvalidInputError(f"neighbors must be in 2..{GRAPH_MAX_K + 1}, got {neighbors}")
+        if not 0.0 <= float(prune) <= 1.0:
+            raise InvalidInputError(f"prune must be in [0, 1], got {prune}")
+        self.neighbors_opt = dict(neighbors=int(neighbors), prune=float(prune))
+
+    def neighbor_result(self, res: EngineResult):
+        """The neighbour graphs of a finished run's matrix (res.allele_freq, the host-merged matrix
+        of every part), on the first device, after the run's engine contexts have closed and
+        after the clustering. Sets res.neighbors and last_timing["neighbors"]; returns the
+        NeighborGraph (None when not enabled)."""
+        if self.neighbors_opt is None:
+            return None
+        from ..analysis.neighbors import neighbor_graph
+
+        t0 = time.perf_counter()
+        try:
+            res.neighbors = neighbor_graph(getattr(res, "allele_freq", None), table=getattr(res, "variants", None),
+                                           device=self.devices[0], **self.neighbors_opt)
+        finally:
+            self.last_timing["neighbors"] = time.perf_counter() - t0
+        return res.neighbors
 
     @staticmethod
     def _population(res: EngineResult) -> np.ndarray:
