@@ -593,6 +593,15 @@ typedef struct mgp_h5_tiles {
 } mgp_h5_tiles;
 int  mgp_h5_tiles_run(mgp_ctx *ctx, mgp_h5_tiles *job, int64_t *total_bytes);
 int  mgp_h5_tiles_fetch(mgp_ctx *ctx, uint8_t *dst, int64_t cap);
+/* The same from caller-supplied u32 rows (counts [n_rows][mito_len][8], tn5
+ * [n_rows][mito_len][2], depth [n_rows][mito_len]) on `device`, no engine context, as
+ * mgp_txt_gz_rows: cell_of_col indexes the rows, values are stored as min(v, 65535) (the
+ * rows are saturated and packed into the run's 16-bit layout on the host, then the run
+ * path's kernels deflate them), the streams go into dst (cap bytes; MGP_E_INVALID with
+ * *total_bytes set and nothing written when it is too small). */
+int  mgp_h5_tiles_rows(int device, const uint32_t *counts, const uint32_t *tn5, const uint32_t *depth,
+                       int32_t n_rows, int32_t mito_len, mgp_h5_tiles *job,
+                       uint8_t *dst, int64_t cap, int64_t *total_bytes);
 /* Variant statistics and heteroplasmy on the device (added under ABI 7). Replaces the R
  * step mgatk users run on counts.h5, identify_variants and calculate_allele_freq
  * (R/mgatk2_functions.R:282-372): reductions over the cells of the run's strand-filtered

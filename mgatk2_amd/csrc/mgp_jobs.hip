@@ -112,8 +112,8 @@ static int on_rows(int device, const char* who, int need, const HostRows& h, Job
     return rc;
 }
 
-// The clustering and graph calls: job(state, stream) on `device` with a stream and a State of
-// the call's own, freed once that stream is idle.
+// The clustering and graph calls, and mgp_h5_tiles_rows: job(state, stream) on `device` with a
+// stream and a State of the call's own, freed once that stream is idle.
 template <class State = ClusterState, class Job>
 static int cl_call(int device, Job&& job) {
     HIP_TRY(hipSetDevice(device));
@@ -292,14 +292,8 @@ int mgp_txt_gz_fetch(mgp_ctx* ctx, uint8_t* dst, int64_t cap) {
 // mgp_h5_tiles: the HDF5 count datasets' chunks deflated on the device
 // (IncrementalHDF5Writer, writers.py:60-131: 11 u16 planes, gzip-4 chunks of 1000 x 100)
 // ---------------------------------------------------------------------------
-int mgp_h5_tiles_run(mgp_ctx* ctx, mgp_h5_tiles* job, int64_t* total_bytes) {
-    using namespace txtgz;
-    if (!ctx || !job) return set_err(MGP_E_INVALID, "null ctx/job");
-    RunRows r;
-    MGP_TRY(run_rows(ctx, "mgp_h5_tiles: no run to write", &r));
-    const int L = r.rows.L;
-    H5State& st = r.jobs->h5;
-    st.total = 0;
+// the arguments of `job` over n_cells rows of L positions (before anything is allocated)
+static int h5_check(const mgp_h5_tiles* job, int L, int32_t n_cells) {
     const int64_t nco = job->n_cols;
     const int crow = job->chunk_rows, ccol = job->chunk_cols;
     if (nco < 0 || crow <= 0 || ccol <= 0 || (int64_t)crow * ccol > (1 << 22) || !job->chunk_bytes ||
@@ -308,17 +302,28 @@ int mgp_h5_tiles_run(mgp_ctx* ctx, mgp_h5_tiles* job, int64_t* total_bytes) {
     const int64_t ncc_all = (nco + ccol - 1) / ccol;
     const int lo = job->col_chunk_lo, hi = job->col_chunk_hi;
     if (lo < 0 || hi < lo || hi > ncc_all) return set_err(MGP_E_INVALID, "mgp_h5_tiles: column chunks out of range");
+    const int64_t nch = (int64_t)txtgz::kPlanes * ((L + crow - 1) / crow) * (hi - lo);
+    if (nch > (int64_t)1 << 20) return set_err(MGP_E_INVALID, "mgp_h5_tiles: too many chunks for one call");
+    if (nch == 0) return MGP_OK;
+    for (int64_t j = 0; j < nco; ++j)
+        if (job->cell_of_col[j] < -1 || job->cell_of_col[j] >= n_cells)
+            return set_err(MGP_E_INVALID, "mgp_h5_tiles: cell of a column out of range");
+    return MGP_OK;
+}
+
+// the streams of `job` from the 16-bit planes c16 / t16 / d16 ([n_cells][L]) into st.packed
+// (st.total bytes; job->chunk_bytes and col_sums filled)
+static int h5_run(H5State& st, hipStream_t s, const uint4* c16, const uint32_t* t16, const uint16_t* d16, int L,
+                  int32_t n_cells, mgp_h5_tiles* job) {
+    using namespace txtgz;
+    st.total = 0;
+    MGP_TRY(h5_check(job, L, n_cells));
+    const int64_t nco = job->n_cols;
+    const int crow = job->chunk_rows, ccol = job->chunk_cols;
+    const int lo = job->col_chunk_lo, hi = job->col_chunk_hi;
     const int nrc = (L + crow - 1) / crow, ncc = hi - lo;
     const int64_t nch = (int64_t)kPlanes * nrc * ncc;
-    if (nch == 0) {
-        if (total_bytes) *total_bytes = 0;
-        return MGP_OK;
-    }
-    if (nch > (int64_t)1 << 20) return set_err(MGP_E_INVALID, "mgp_h5_tiles: too many chunks for one call");
-    for (int64_t j = 0; j < nco; ++j)
-        if (job->cell_of_col[j] < -1 || job->cell_of_col[j] >= r.n_cells)
-            return set_err(MGP_E_INVALID, "mgp_h5_tiles: cell of a column out of range");
-    hipStream_t s = r.stream;
+    if (nch == 0) return MGP_OK;
     const uint64_t chunk_raw = (uint64_t)crow * ccol * 2, stride = out_bound(chunk_raw);
     const uint64_t raw_stride = (chunk_raw + 15) & ~uint64_t(15);
     MGP_TRY(st.coc.ensure((size_t)std::max<int64_t>(nco, 1) * 4));
@@ -334,7 +339,7 @@ int mgp_h5_tiles_run(mgp_ctx* ctx, mgp_h5_tiles* job, int64_t* total_bytes) {
     for (int64_t k = 0; k < nch; ++k) oo[(size_t)k] = (uint64_t)k * stride;
     if (nco) HIP_TRY(hipMemcpyAsync(st.coc.p, job->cell_of_col, (size_t)nco * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(st.out_off.p, oo.data(), (size_t)nch * 8, hipMemcpyHostToDevice, s));
-    H5Job jb{r.rows.c16, r.tn5.t16, r.rows.d16, L, st.coc.as<int32_t>(), nco, crow, ccol, nrc, lo, ncc,
+    H5Job jb{c16, t16, d16, L, st.coc.as<int32_t>(), nco, crow, ccol, nrc, lo, ncc,
              st.sums.as<unsigned long long>()};
     H5Scratch sc{st.raw.as<uint8_t>(), st.tok.as<uint32_t>(), st.out.as<uint32_t>(), st.out_off.as<uint64_t>(),
                  st.chunk_bytes.as<uint32_t>(), chunk_raw, stride, raw_stride, h5_tok_words(chunk_raw), nullptr};
@@ -381,7 +386,15 @@ int mgp_h5_tiles_run(mgp_ctx* ctx, mgp_h5_tiles* job, int64_t* total_bytes) {
         return set_err(MGP_E_HIP, "mgp_h5_tiles: pack kernel launch failed");
     HIP_TRY(hipStreamSynchronize(s));
     st.total = tot;
-    if (total_bytes) *total_bytes = (int64_t)tot;
+    return MGP_OK;
+}
+
+int mgp_h5_tiles_run(mgp_ctx* ctx, mgp_h5_tiles* job, int64_t* total_bytes) {
+    if (!ctx || !job) return set_err(MGP_E_INVALID, "null ctx/job");
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_h5_tiles: no run to write", &r));
+    MGP_TRY(h5_run(r.jobs->h5, r.stream, r.rows.c16, r.tn5.t16, r.rows.d16, r.rows.L, r.n_cells, job));
+    if (total_bytes) *total_bytes = (int64_t)r.jobs->h5.total;
     return MGP_OK;
 }
 
@@ -393,6 +406,46 @@ int mgp_h5_tiles_fetch(mgp_ctx* ctx, uint8_t* dst, int64_t cap) {
     HIP_TRY(hipSetDevice(device));
     if (jobs->h5.total) HIP_TRY(hipMemcpy(dst, jobs->h5.packed.p, jobs->h5.total, hipMemcpyDeviceToHost));
     return MGP_OK;
+}
+
+// The caller's u32 rows saturated and packed on the host into the run's 16-bit layout (one
+// uint4 of (fwd | rev << 16) pairs, one tn5 word and one u16 depth per position), uploaded,
+// and h5_run on them under a stream and a state of the call's own (cl_call).
+int mgp_h5_tiles_rows(int device, const uint32_t* counts, const uint32_t* tn5, const uint32_t* depth, int32_t n_rows,
+                      int32_t mito_len, mgp_h5_tiles* job, uint8_t* dst, int64_t cap, int64_t* total_bytes) {
+    const std::string who = "mgp_h5_tiles_rows";
+    if (!job || n_rows < 0 || mito_len <= 0 || (n_rows > 0 && (!counts || !tn5 || !depth)))
+        return set_err(MGP_E_INVALID, who + ": bad arguments");
+    return cl_call<H5State>(device, [&](H5State& st, hipStream_t s) {
+        MGP_TRY(h5_check(job, mito_len, n_rows));
+        const size_t npos = (size_t)n_rows * (size_t)mito_len;
+        std::vector<uint32_t> c16(npos * 4), t16(npos);
+        std::vector<uint16_t> d16(npos);
+        auto sat = [](uint32_t v) -> uint32_t { return v < 65535u ? v : 65535u; };
+        for (size_t P = 0; P < npos; ++P) {
+            for (int q = 0; q < 4; ++q)
+                c16[4 * P + q] = sat(counts[8 * P + 2 * q]) | sat(counts[8 * P + 2 * q + 1]) << 16;
+            t16[P] = sat(tn5[2 * P]) | sat(tn5[2 * P + 1]) << 16;
+            d16[P] = (uint16_t)sat(depth[P]);
+        }
+        DevBuf bc, bt, bd;
+        MGP_TRY(bc.ensure(npos * 16 + 64));
+        MGP_TRY(bt.ensure(npos * 4 + 64));
+        MGP_TRY(bd.ensure(npos * 2 + 64));
+        if (npos && (hipMemcpy(bc.p, c16.data(), npos * 16, hipMemcpyHostToDevice) != hipSuccess ||
+                     hipMemcpy(bt.p, t16.data(), npos * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                     hipMemcpy(bd.p, d16.data(), npos * 2, hipMemcpyHostToDevice) != hipSuccess))
+            return set_err(MGP_E_HIP, who + ": upload failed");
+        const int rc = h5_run(st, s, bc.as<uint4>(), bt.as<uint32_t>(), bd.as<uint16_t>(), mito_len, n_rows, job);
+        (void)hipStreamSynchronize(s);  // (before the rows' buffers go)
+        if (rc != MGP_OK) return rc;
+        if (total_bytes) *total_bytes = (int64_t)st.total;
+        if ((int64_t)st.total > cap) return set_err(MGP_E_INVALID, who + ": destination too small");
+        if (st.total && !dst) return set_err(MGP_E_INVALID, who + ": bad arguments");
+        if (st.total && hipMemcpy(dst, st.packed.p, st.total, hipMemcpyDeviceToHost) != hipSuccess)
+            return set_err(MGP_E_HIP, who + ": download failed");
+        return (int)MGP_OK;
+    });
 }
 
 int mgp_txt_gz_rows(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,

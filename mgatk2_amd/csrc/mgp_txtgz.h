@@ -100,10 +100,27 @@ struct H5Scratch {
     uint64_t tok_stride;     // h5_tok_words(chunk_raw)
     uint64_t* prof;          // MGP_H5_PROF: [chunks][4] phase stamps (100 MHz wall clock), else null
 };
-// a chunk's parse segment (bytes per thread, 16-aligned) and its token words (u16 tokens,
-// at most two segments' worth per thread)
-__host__ __device__ inline int h5_seg_bytes(uint64_t chunk_raw) { return (int)((((chunk_raw + 255) / 256) + 15) & ~uint64_t(15)); }
-__host__ __device__ inline uint64_t h5_tok_words(uint64_t chunk_raw) { return (uint64_t)h5_seg_bytes(chunk_raw) * 256; }
+// a chunk's parse segment (bytes per thread, 16-aligned), the threads that own bytes, and
+// its token words (u16 tokens, per owning thread at most two segments' worth and no more
+// than the chunk has bytes). A run is one thread's only as far as the head of the next
+// segment, so a segment is never shorter than kH5MinSeg bytes: the longest match (258) fits
+// in it, and a long run in a small chunk is tokens of 258, not one of 16 per thread. Chunks
+// of 69,632 bytes and more, the reference's 1000 x 100 among them, have longer segments
+// anyway and all 256 threads own bytes; in smaller ones the last threads own nothing.
+constexpr int kH5MinSeg = 272;
+__host__ __device__ inline int h5_seg_bytes(uint64_t chunk_raw) {
+    const int p = (int)((((chunk_raw + 255) / 256) + 15) & ~uint64_t(15));
+    return p < kH5MinSeg ? kH5MinSeg : p;
+}
+__host__ __device__ inline int h5_seg_threads(uint64_t chunk_raw) {
+    const uint64_t p = (uint64_t)h5_seg_bytes(chunk_raw);
+    const uint64_t n = (chunk_raw + p - 1) / p;
+    return n ? (int)n : 1;
+}
+__host__ __device__ inline uint64_t h5_tok_words(uint64_t chunk_raw) {
+    const uint64_t per_thread = 2 * (uint64_t)h5_seg_bytes(chunk_raw);
+    return ((per_thread < chunk_raw ? per_thread : chunk_raw) * (uint64_t)h5_seg_threads(chunk_raw) + 1) / 2;
+}
 // the planes' raw chunks of the batch, then their zlib streams (chunk_bytes filled)
 int h5_deflate(const H5Job& job, const H5Scratch& sc, hipStream_t s);
 // the streams packed back to back (chunk order) into dst at dst_off[chunks]

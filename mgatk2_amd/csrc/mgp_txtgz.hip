@@ -983,11 +983,18 @@ __device__ uint64_t deflate_block(CodeLds& S, const uint8_t* T, const Tok& tok, 
         if (t == kT - 1) bw.put(S.lit_code[256], S.lit_len[256]);
         bw.done();
     } else if (mode == 1) {
-        // the fixed codes (RFC 1951 3.2.6), canonical from their lengths
+        // the fixed codes (RFC 1951 3.2.6). The literal/length code is canonical over 288
+        // symbols: 286 and 287 never occur but hold two 8-bit codes, so canon() over the kLit
+        // symbols here would start the 9-bit codes of the bytes 144..255 four too low; the
+        // codes are taken from the table's four ranges instead
         if (t == 0) {
-            for (int s = 0; s < 288 && s < kLit; ++s) S.lit_len[s] = fixed_len(s);
+            for (int s = 0; s < kLit; ++s) {
+                const int l = fixed_len(s);
+                const uint32_t c = s < 144 ? 0x30u + s : s < 256 ? 0x190u + (s - 144) : s < 280 ? s - 256 : 0xC0u + (s - 280);
+                S.lit_len[s] = (uint8_t)l;
+                S.lit_code[s] = (uint16_t)(__brev(c) >> (32 - l));
+            }
             for (int s = 0; s < kDist; ++s) S.dist_len[s] = 5;
-            canon(S.lit_len, kLit, S.lit_code);
             canon(S.dist_len, kDist, S.dist_code);
             BitW bw(out, 8 * (uint64_t)hdr_len);
             bw.put(1, 1);
@@ -1202,11 +1209,13 @@ __global__ void __launch_bounds__(kT) k_h5_code(H5Job job, H5Scratch sc) {
     int pend = 0;
     int pv = t0 > 0 ? (int)T[t0 - 1] : -1;
     // the tokens as u16 (a literal byte, or 256 + length - 3 of a distance-1 match), the
-    // thread's q-th at tok16[q kT + t]: each wave's loads and stores of its q-th tokens are
-    // one contiguous range (the thread-contiguous layout cost 0.6 ms per chunk in each
-    // pass over the tokens: 64 lines per wave access)
+    // thread's q-th at tok16[q nT + t], nT the threads that own bytes (kT unless the chunk is
+    // small): each wave's loads and stores of its q-th tokens are one contiguous range (the
+    // thread-contiguous layout cost 0.6 ms per chunk in each pass over the tokens: 64 lines
+    // per wave access)
     uint16_t* const tok16 = reinterpret_cast<uint16_t*>(tok);
-    auto put = [&](uint32_t v) { tok16[(size_t)ntok++ * kT + t] = (uint16_t)v; };
+    const size_t nT = (size_t)h5_seg_threads(sc.chunk_raw);
+    auto put = [&](uint32_t v) { tok16[(size_t)ntok++ * nT + t] = (uint16_t)v; };
     auto flush = [&]() {
         if (pend >= 3) {
             atomicAdd(&S.lit_f[257 + len_code(pend)], 1u);
@@ -1254,7 +1263,7 @@ __global__ void __launch_bounds__(kT) k_h5_code(H5Job job, H5Scratch sc) {
     const uint8_t zhdr[2] = {0x78, 0x5E};
     H5_STAMP(2);
     auto tok_of = [&](uint32_t q) -> uint32_t {
-        const uint32_t v = tok16[(size_t)q * kT + t];
+        const uint32_t v = tok16[(size_t)q * nT + t];
         return v < 256u ? v : ((v - 253u) << 16) | 1u;  // (length v - 256 + 3, distance 1)
     };
     const uint64_t blk = deflate_block(S, T, tok_of, ntok, (uint64_t)n, out, zhdr, 2, sc.prof ? sc.prof + k * 8 + 4 : nullptr);

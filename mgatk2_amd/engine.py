@@ -40,7 +40,7 @@ ABI_SYMBOLS = (
     "mgp_download_inputs", "mgp_set_stage_timing", "mgp_fetch_cells", "mgp_fetch_rows16", "mgp_windows",
     "mgp_stream_info", "mgp_set_streaming", "mgp_set_rows16_target", "mgp_copy_wait", "mgp_set_cell_range",
     "mgp_push_batch16", "mgp_txt_gz_run", "mgp_txt_gz_fetch", "mgp_txt_gz_rows", "mgp_set_rows_target",
-    "mgp_h5_tiles_run", "mgp_h5_tiles_fetch", "mgp_variant_moments_run", "mgp_variant_dev2_run",
+    "mgp_h5_tiles_run", "mgp_h5_tiles_fetch", "mgp_h5_tiles_rows", "mgp_variant_moments_run", "mgp_variant_dev2_run",
     "mgp_allele_freq_run", "mgp_variant_moments_rows", "mgp_variant_dev2_rows", "mgp_allele_freq_rows",
     "mgp_cell_coverage_run", "mgp_position_coverage_run", "mgp_position_depth_hist_run",
     "mgp_position_depth_next_run", "mgp_cell_coverage_rows", "mgp_position_coverage_rows",
@@ -288,6 +288,9 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_h5_tiles_run": ([vp, C.POINTER(mgp_h5_tiles), C.POINTER(i64)], C.c_int),
         "mgp_h5_tiles_fetch": ([vp, vp, i64], C.c_int),
         "mgp_txt_gz_fetch": ([vp, vp, i64], C.c_int),
+        "mgp_h5_tiles_rows": (
+            [C.c_int, vp, vp, vp, i32, i32, C.POINTER(mgp_h5_tiles), vp, i64, C.POINTER(i64)], C.c_int
+        ),
         "mgp_txt_gz_rows": ([C.c_int, vp, vp, i32, i32, C.POINTER(mgp_txt_gz), vp, i64, C.POINTER(i64)], C.c_int),
         "mgp_variant_moments_run": ([vp, C.POINTER(mgp_variant_job), C.POINTER(mgp_variant_moments)], C.c_int),
         "mgp_variant_dev2_run": ([vp, C.POINTER(mgp_variant_job), vp, vp], C.c_int),
@@ -514,9 +517,10 @@ class TxtMembers:
         return self.blob[a:a + int(per[f])]
 
 
-def _txt_job(cells, names: list[str]):
+def _txt_job(cells, names: list):
+    """(names: str, or bytes taken as they are)"""
     cells = np.ascontiguousarray(cells, dtype=np.int32)
-    enc = [n.encode() for n in names]
+    enc = [bytes(n) if isinstance(n, (bytes, bytearray)) else n.encode() for n in names]
     if len(enc) != cells.shape[0]:
         raise InvalidInputError("one barcode per written cell")
     off = np.zeros(len(enc) + 1, np.int64)
@@ -540,7 +544,9 @@ def txt_gz_rows(counts: np.ndarray, depth: np.ndarray, cells, names: list[str], 
         raise InvalidInputError("counts must be [n, L, 8]")
     job, keep, mb, tb = _txt_job(cells, names)
     # a bound: every member's text (<= bc + 29 bytes per covered position) plus stored-block overhead
-    nnz = np.count_nonzero(depth, axis=1)[np.asarray(keep[0], np.int64)] if len(names) else np.zeros(0, np.int64)
+    # (a cell out of range is the library's to refuse: it only has to get a bound here)
+    rows = np.clip(np.asarray(keep[0], np.int64), 0, max(0, n_rows - 1))
+    nnz = np.count_nonzero(depth, axis=1)[rows] if len(names) and n_rows else np.zeros(len(names), np.int64)
     text = nnz.astype(np.int64) * (np.diff(keep[2]) + 29)
     cap = int((5 * (text + 5 * (text // 65535 + 1) + 96)).sum()) + 64
     out = np.empty(cap, np.uint8)
@@ -548,6 +554,48 @@ def txt_gz_rows(counts: np.ndarray, depth: np.ndarray, cells, names: list[str], 
     _ck(lib.mgp_txt_gz_rows(int(device), _ptr(counts), _ptr(depth), int(n_rows), int(L), C.byref(job), _ptr(out), cap,
                             C.byref(tot)), "mgp_txt_gz_rows")
     return TxtMembers(out[:int(tot.value)], mb, tb)
+
+
+def _h5_grid(streams: np.ndarray, cb: np.ndarray, nrc: int, ncc: int) -> dict:
+    """{plane: [chunk streams, row-major over an nrc x ncc grid]}: views of `streams`, which
+    holds them plane-major with sizes cb."""
+    offs = np.concatenate([[0], np.cumsum(cb)]).tolist()
+    return {p: [streams[offs[k]:offs[k + 1]] for k in range(i * nrc * ncc, (i + 1) * nrc * ncc)]
+            for i, p in enumerate(H5_PLANES)}
+
+
+def h5_tiles_rows(counts: np.ndarray, tn5: np.ndarray, depth: np.ndarray, cell_of_col, chunks: tuple[int, int],
+                  col_chunks: tuple[int, int] | None = None, sums: dict | None = None, device: int = 0) -> dict:
+    """mgp_h5_tiles_rows: what Engine.h5_tiles returns, from caller-supplied u32 rows (counts
+    [n, L, 8], tn5 [n, L, 2], depth [n, L]; stored as min(v, 65535)), no engine context;
+    cell_of_col indexes the rows. One call covers all of col_chunks."""
+    lib = load_library()
+    counts = np.ascontiguousarray(counts, np.uint32)
+    tn5 = np.ascontiguousarray(tn5, np.uint32)
+    depth = np.ascontiguousarray(depth, np.uint32)
+    n_rows, L = depth.shape
+    if counts.shape != (n_rows, L, 8) or tn5.shape != (n_rows, L, 2):
+        raise InvalidInputError("counts must be [n, L, 8] and tn5 [n, L, 2]")
+    coc = np.ascontiguousarray(cell_of_col, np.int32)
+    crow, ccol = int(chunks[0]), int(chunks[1])
+    if crow <= 0 or ccol <= 0:
+        raise InvalidInputError("chunk shape must be positive")
+    nrc = -(-L // crow)
+    c0, c1 = (0, -(-coc.size // ccol)) if col_chunks is None else (int(col_chunks[0]), int(col_chunks[1]))
+    nch = len(H5_PLANES) * nrc * max(0, c1 - c0)
+    cb = np.zeros(max(1, nch), np.int64)
+    part = np.zeros((3, L), np.int64)
+    job = mgp_h5_tiles(coc.size, _ptr(coc), crow, ccol, c0, c1, _ptr(cb), _ptr(part))
+    # a bound: every chunk stored, with the frame (the device's own bound is no larger)
+    raw = 2 * crow * ccol
+    cap = nch * (raw + 5 * (raw // 65535 + 1) + 6) if crow * ccol <= 1 << 22 else 0
+    out = np.empty(max(1, cap), np.uint8)
+    tot = C.c_int64()
+    _ck(lib.mgp_h5_tiles_rows(int(device), _ptr(counts), _ptr(tn5), _ptr(depth), int(n_rows), int(L), C.byref(job),
+                              _ptr(out), cap, C.byref(tot)), "mgp_h5_tiles_rows")
+    if sums is not None:
+        sums.update(coverage=part[0].copy(), tn5_fwd=part[1].copy(), tn5_rev=part[2].copy())
+    return _h5_grid(out[:int(tot.value)], cb[:nch], nrc, c1 - c0)
 
 
 VARIANT_MAX_CELLS = 1 << 16  # cells of one mgp_variant_* call (the u64 moments' exactness bound)

@@ -199,7 +199,7 @@ def test_row_jobs_refuse_null_arguments_before_any_device_call():
     *_run forms a null context, with MGP_E_INVALID and their own message, before any device
     call (so this runs without a device). Planes read: depth alone for the cell coverage and
     the two depth passes, counts + tn5 + depth for the position coverage, counts + depth for
-    the txt writer and the variant forms."""
+    the txt writer and the variant forms, counts + tn5 + depth for the HDF5 chunks."""
     from mgatk2_amd import engine
     from mgatk2_amd.build import build_engine
 
@@ -218,6 +218,7 @@ def test_row_jobs_refuse_null_arguments_before_any_device_call():
     # name -> (the planes it takes, in argument order; the arguments after mito_len)
     detached = {
         "mgp_txt_gz_rows": (("counts", "depth"), (job, None, 0, None)),
+        "mgp_h5_tiles_rows": (("counts", "tn5", "depth"), (engine.mgp_h5_tiles(), None, 0, None)),
         "mgp_variant_moments_rows": (("counts", "depth"), (None, None)),
         "mgp_variant_dev2_rows": (("counts", "depth"), (None, None, None)),
         "mgp_allele_freq_rows": (("counts", "depth"), (None, 0, None, None, 0, None)),
@@ -233,6 +234,11 @@ def test_row_jobs_refuse_null_arguments_before_any_device_call():
             refused(name, f"{name}: bad arguments", 0, *ptrs, n_rows, mito_len, *rest)
     refused("mgp_txt_gz_rows", "mgp_txt_gz_rows: bad arguments", 0, planes["counts"].ctypes.data,
             planes["depth"].ctypes.data, n_rows, 0, job, None, 0, None)
+
+    all3 = [planes[p].ctypes.data for p in ("counts", "tn5", "depth")]
+    refused("mgp_h5_tiles_rows", "mgp_h5_tiles_rows: bad arguments", 0, *all3, n_rows, mito_len, None, None, 0, None)
+    refused("mgp_h5_tiles_rows", "mgp_h5_tiles_rows: bad arguments", 0, *all3, n_rows, 0, engine.mgp_h5_tiles(), None,
+            0, None)
 
     refused("mgp_txt_gz_run", "null ctx/job", None, job, None)
     refused("mgp_h5_tiles_run", "null ctx/job", None, engine.mgp_h5_tiles(), None)
