@@ -34,6 +34,7 @@ from pathlib import Path
 import numpy as np
 
 from ..exceptions import InvalidInputError
+from ..shard import DeviceParts
 
 NAN = float("nan")
 NONE_NEXT = 0xFFFFFFFF  # position_depth_next: no depth above v
@@ -253,16 +254,15 @@ def merge_position(parts: list[dict], L: int) -> dict:
 
 def _position_pass(parts, cells: np.ndarray, L: int):
     """(merged position integers, mid_lo, mid_hi) of the population `cells` over the parts."""
-    from .variants import _per_part, _split
-
-    calls = _split(parts, cells)
+    parts = DeviceParts(parts)
+    calls = parts.split(cells)
     n = int(cells.size)
     if n == 0:
         z = np.zeros(L, np.uint32)
         return merge_position([], L), z, z
 
     def every(fn):  # fn(engine, local) for every call of every part, the devices concurrently
-        got = _per_part(parts, lambda d: [fn(parts[d][0], loc) for _, loc in calls[d]])
+        got = parts.map(lambda d: [fn(parts[d][0], loc) for _, loc in calls[d]])
         return [x for g in got for x in g]
 
     pos = merge_position(every(lambda e, loc: e.position_coverage(loc)), L)
@@ -292,19 +292,16 @@ def run_coverage(source, cells=None, min_mean_coverage: float = 0.0, min_coverag
     Calls are split at VARIANT_MAX_CELLS cells and the parts run concurrently; the host adds
     the integers, combines the max / min and puts the cell rows in population order."""
     from ..engine import CELL_COVERAGE_FIELDS
-    from .variants import _as_parts, _per_part, _split
 
-    parts = _as_parts(source)
+    parts = DeviceParts(source)
     L = int(parts[0][0].cfg.mito_len)
     t0 = time.perf_counter()
-    if cells is None:
-        cells = np.concatenate([np.arange(lo, hi, dtype=np.int64) for _, lo, hi in parts])
-    cells = np.asarray(cells, np.int64).reshape(-1)
+    cells = parts.all_cells() if cells is None else np.asarray(cells, np.int64).reshape(-1)
     n = int(cells.size)
     raw = {k: np.zeros(n, dt) for k, dt in CELL_COVERAGE_FIELDS}
     if n:
-        calls = _split(parts, cells)
-        for got in _per_part(parts, lambda d: [(ix, parts[d][0].cell_coverage(loc)) for ix, loc in calls[d]]):
+        calls = parts.split(cells)
+        for got in parts.map(lambda d: [(ix, parts[d][0].cell_coverage(loc)) for ix, loc in calls[d]]):
             for ix, block in got:
                 for k in raw:
                     raw[k][ix] = block[k]

@@ -27,8 +27,9 @@ from pathlib import Path
 
 import numpy as np
 
-from ..engine import MOMENT_FIELDS, VARIANT_MAX_CELLS, Engine
+from ..engine import MOMENT_FIELDS
 from ..exceptions import InvalidInputError
+from ..shard import DeviceParts
 
 BASES = "ACGT"
 TSV_COLUMNS = ("position", "nucleotide", "variant", "mean", "vmr", "n_cells_detected", "n_cells_conf_detected",
@@ -159,45 +160,6 @@ def variant_table(moments: dict, dev2: np.ndarray, ref_alleles: list[str], n: in
 
 # ---- the device passes over one or several contexts ---------------------------------
 
-def _as_parts(source) -> list[tuple]:
-    if isinstance(source, Engine):
-        return [(source, 0, source.cfg.n_cells)]
-    parts = [(e, int(lo), int(hi)) for e, lo, hi in source]
-    if not parts:
-        raise InvalidInputError("identify_variants: no device parts")
-    return parts
-
-
-def _split(parts, cells: np.ndarray):
-    """The population split over the parts: per part, the indices into `cells` it owns (in
-    order) and their part-local cell indices, in calls of at most VARIANT_MAX_CELLS cells.
-    The all-zero rows (-1) go with the first part."""
-    calls = []
-    for d, (_, lo, hi) in enumerate(parts):
-        own = (cells >= lo) & (cells < hi)
-        if d == 0:
-            own |= cells < 0
-        idx = np.flatnonzero(own)
-        local = np.where(cells[idx] >= 0, cells[idx] - lo, -1).astype(np.int32)
-        chunks = [(idx[a:a + VARIANT_MAX_CELLS], local[a:a + VARIANT_MAX_CELLS])
-                  for a in range(0, idx.size, VARIANT_MAX_CELLS)]
-        calls.append(chunks)
-    covered = sum(ix.size for ch in calls for ix, _ in ch)
-    if covered != cells.size:
-        raise InvalidInputError("identify_variants: a cell of the population is on no device part")
-    return calls
-
-
-def _per_part(parts, fn) -> list:
-    """fn(d) for every part, the devices concurrently (ctypes releases the GIL)."""
-    if len(parts) == 1:
-        return [fn(0)]
-    from concurrent.futures import ThreadPoolExecutor
-
-    with ThreadPoolExecutor(len(parts)) as pool:
-        return list(pool.map(fn, range(len(parts))))
-
-
 @dataclass
 class VariantResult:
     table: VariantTable
@@ -218,21 +180,19 @@ def run_variants(source, ref_alleles: list[str] | None = None, cells=None, min_c
     every cell of the parts. `ref_alleles`: default ref_alleles() of the parts' summed tally."""
     from ..file_io.writers import ref_alleles as ref_of
 
-    parts = _as_parts(source)
+    parts = DeviceParts(source)
     t0 = time.perf_counter()
-    if cells is None:
-        cells = np.concatenate([np.arange(lo, hi, dtype=np.int64) for _, lo, hi in parts])
-    cells = np.asarray(cells, np.int64)
+    cells = parts.all_cells() if cells is None else np.asarray(cells, np.int64)
     n = int(cells.size)
     thr = int(low_coverage_threshold) if stabilize_variance else 0
     if ref_alleles is None:
         ref_alleles = ref_of(sum(e.fetch(dense=False).ref_tally.astype(np.int64) for e, _, _ in parts))
-    calls = _split(parts, cells)
+    calls = parts.split(cells)
 
     def pass1(d):
         return [parts[d][0].variant_moments(loc, thr) for _, loc in calls[d]]
 
-    mom = merge_moments([m for ms in _per_part(parts, pass1) for m in ms] or
+    mom = merge_moments([m for ms in parts.map(pass1) for m in ms] or
                         [parts[0][0].variant_moments(np.zeros(0, np.int32), thr)])
     t1 = time.perf_counter()
     mu = mean_af(mom, n)
@@ -241,7 +201,7 @@ def run_variants(source, ref_alleles: list[str] | None = None, cells=None, min_c
         return [parts[d][0].variant_dev2(mu, loc, thr) for _, loc in calls[d]]
 
     dev2 = np.zeros_like(mu)
-    for ds in _per_part(parts, pass2):
+    for ds in parts.map(pass2):
         for x in ds:
             dev2 += x
     t2 = time.perf_counter()
@@ -256,7 +216,7 @@ def run_variants(source, ref_alleles: list[str] | None = None, cells=None, min_c
             def gather(d):
                 return [(ix, parts[d][0].allele_freq(pairs, loc, min_coverage)) for ix, loc in calls[d]]
 
-            for got in _per_part(parts, gather):
+            for got in parts.map(gather):
                 for ix, block in got:
                     af[:, ix] = block
     t4 = time.perf_counter()
@@ -273,7 +233,7 @@ def identify_variants(source, ref_alleles: list[str] | None = None, cells=None, 
     min_strand_cor=0.65, min_vmr=0.01."""
     if hasattr(source, "last_result") and hasattr(source, "enable_variants"):
         res = source.last_result
-        if res is None or getattr(res, "variants", None) is None:
+        if res is None or res.variants is None:
             raise InvalidInputError("identify_variants: the processor's last run did not call variants "
                                     "(enable_variants before the run)")
         return res.variants

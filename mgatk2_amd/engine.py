@@ -398,6 +398,16 @@ class EngineResult:
     first_read: np.ndarray
     ref_tally: np.ndarray  # [L, 4] u64
     stats: dict
+    # what a CellProcessor run adds (None: that step was not enabled, or has not run)
+    txt_gz_cells: np.ndarray | None = None  # the device txt writer: the cells whose count lines it wrote [n written]
+    h5_tiles: tuple | None = None  # the device HDF5 writer: (cell of column [n], chunks, {plane: tiles}, column sums)
+    coverage: object | None = None  # enable_coverage: the CoverageResult over every cell of the run
+    variants: object | None = None  # enable_variants: the VariantTable
+    allele_freq: np.ndarray | None = None  # enable_variants: f64 [n variants, n population cells]
+    variant_cells: np.ndarray | None = None  # enable_variants after enable_coverage: allele_freq's columns [n kept]
+    variant_seconds: dict | None = None  # enable_variants: run_variants' seconds by pass
+    clusters: object | None = None  # cluster_result: the ClusterResult
+    neighbors: object | None = None  # neighbor_result: the NeighborGraph
 
     @staticmethod
     def alloc(n_cells: int, L: int, dense: bool = True) -> EngineResult:

@@ -138,7 +138,7 @@ class IncrementalTextWriter:
             q = cell_qc(res, c, names[c], L)
             self.cell_stats.append(q)
             self.cell_depths[names[c]] = q["mean_depth"]
-        done = getattr(res, "txt_gz_cells", None)
+        done = res.txt_gz_cells
         if done is None or not np.array_equal(np.asarray(done, np.int64), cells):
             txt_write_cells(self.prefix, res.counts, res.depth, cells, [names[c] for c in cells.tolist()],
                             level=self.gzip_level, n_threads=self.n_threads)
@@ -318,7 +318,7 @@ class IncrementalHDF5Writer:
         (cell_of_col, chunks, tiles, column sums)) when they are of these columns and chunks."""
         if len(self._sources) != 1:
             return None
-        dev = getattr(self._sources[0][0], "h5_tiles", None)
+        dev = self._sources[0][0].h5_tiles
         if dev is None or tuple(dev[1]) != tuple(chunks) or not np.array_equal(dev[0], coc):
             return None
         return dev

@@ -259,7 +259,7 @@ class MtDNAPipeline:
         meta = QCCalculator(self.config).collect_run_metadata(
             str(self.bam_path), str(self.output_dir), n_cells_input, len(cell_results))
         write_run_summary(meta, qc_dir / "summary.txt")
-        cov = getattr(res, "coverage", None) if self.coverage_on else None
+        cov = res.coverage if self.coverage_on else None
         if cov is not None and (self.coverage_stats or cov.ref_alleles is not None):
             from .analysis.coverage import write_coverage_outputs
             from .file_io.writers import ref_alleles
@@ -267,12 +267,13 @@ class MtDNAPipeline:
             write_coverage_outputs(cov, self.barcode_list, self.output_dir, ref_alleles(res.ref_tally),
                                    tables=self.coverage_stats)
             logger.info("%d of %d cells kept by the coverage filter", int(cov.kept.sum()), int(cov.kept.size))
-        if self.call_variants and getattr(res, "variants", None) is not None:
+        # the barcodes of the heteroplasmy matrix's columns (the coverage filter's kept cells, if it ran)
+        af_names = self.barcode_list if res.variant_cells is None else \
+            [self.barcode_list[int(i)] for i in res.variant_cells]
+        if self.call_variants and res.variants is not None:
             from .analysis.variants import write_variant_outputs
 
-            kept = getattr(res, "variant_cells", None)  # (the coverage filter's kept cells: the matrix's columns)
-            names = self.barcode_list if kept is None else [self.barcode_list[int(i)] for i in kept]
-            write_variant_outputs(res.variants, res.allele_freq, names, self.output_dir, self.output_format)
+            write_variant_outputs(res.variants, res.allele_freq, af_names, self.output_dir, self.output_format)
             logger.info("%d variants called", len(res.variants))
         t3 = time.time()
         gc.collect()
@@ -291,25 +292,21 @@ class MtDNAPipeline:
             except Exception as e:
                 logger.warning("Failed to generate HTML report: %s", e)
         t4 = time.time()
-        if self.cluster and getattr(res, "variants", None) is not None:
+        if self.cluster and res.variants is not None:
             # last, so that a population above the clustering's bound raises with every other
             # output written; the run's engine contexts closed long ago
             from .analysis.clustering import write_cluster_outputs
 
-            kept = getattr(res, "variant_cells", None)
-            names = self.barcode_list if kept is None else [self.barcode_list[int(i)] for i in kept]
             clusters = processor.cluster_result(res)
-            write_cluster_outputs(clusters, names, res.variants, self.output_dir)
+            write_cluster_outputs(clusters, af_names, res.variants, self.output_dir)
             if clusters.cells is not None:
                 logger.info("Clustered %d cells and %d variants", clusters.cells.n, clusters.variants.n)
-        if self.neighbors is not None and getattr(res, "variants", None) is not None:
+        if self.neighbors is not None and res.variants is not None:
             # after the clustering, for the same reason
             from .analysis.neighbors import write_neighbor_outputs
 
-            kept = getattr(res, "variant_cells", None)
-            names = self.barcode_list if kept is None else [self.barcode_list[int(i)] for i in kept]
             graph = processor.neighbor_result(res)
-            write_neighbor_outputs(graph, names, self.output_dir)
+            write_neighbor_outputs(graph, af_names, self.output_dir)
             if graph.idx is not None:
                 logger.info("Neighbour graph: %d cells, k.param %d, %d SNN edges", graph.n, graph.k_param,
                             int(graph.i.size))

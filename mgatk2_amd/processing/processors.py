@@ -24,9 +24,12 @@ from queue import Queue
 
 import numpy as np
 
-from ..engine import TXT_FILES, Engine, EngineResult, PinnedBuffer, Rows16
+from ..engine import Engine, EngineResult, PinnedBuffer, Rows16
 from ..exceptions import InvalidInputError
+from ..shard import (DeviceParts, copy_part, merge_results, merged_stats, partition_cells, reads_per_cell,
+                     shard_soa)
 from ..synth import ReadSoA, pack_reads
+from .device_writers import write_h5, write_txt
 from .pileup import result_dict, simple_reads_to_dicts
 
 logger = logging.getLogger(__name__)
@@ -37,8 +40,6 @@ MP_CONTEXT = "spawn"  # kept for API compatibility (processors.py:17); no proces
 # MGP_STREAM_SLOTS override them, read at each run)
 STREAM_BATCH_READS = 4_000_000
 STREAM_SLOTS = 3
-# cells per mgp_txt_gz call (its device scratch is ~7 GB per 1000 C4 cells)
-TXT_CHUNK_CELLS = 2048
 
 
 def _engine_config_for(config, n_cells: int, dedup: bool):
@@ -103,6 +104,46 @@ def _payload_hint(n_reads: int, n_cells: int = 0, batch_reads: int = STREAM_BATC
     return int(n_reads) * 64 + ranges * (int(n_cells) + 2) * 64 + (64 << 20)
 
 
+def _rows_slice(r: Rows16, lo: int, hi: int) -> Rows16:
+    """The cells [lo, hi) of 16-bit rows, as views."""
+    return Rows16(r.counts[lo:hi], r.tn5[lo:hi], r.depth[lo:hi], r.wide[lo:hi], r.window_width)
+
+
+class _RowsTarget:
+    """The rows target of a streamed run: pinned 16-bit result rows for all n_cells cells
+    (GBs of pinned memory: ~0.25 s per GB to pin), allocated on a thread of its own while the
+    first batches go in. The engine copies the rows of the windows piled before its target is
+    set when it is set (ABI 4). `windows`: the engine's windows()."""
+
+    def __init__(self, n_cells: int, L: int, windows: tuple[int, int]):
+        self._rows, self._err = None, None
+        self._thread = threading.Thread(target=self._alloc, args=(n_cells, L, *windows), name="mgp-rows-alloc",
+                                        daemon=True)
+        self._thread.start()
+
+    def _alloc(self, n_cells, L, nw, W):
+        try:
+            if n_cells > 0:
+                rb = PinnedBuffer(n_cells * L * 22 + n_cells * nw + 4096)
+                self._rows = Rows16(
+                    rb.array((n_cells, L, 8), np.uint16, 0), rb.array((n_cells, L, 2), np.uint16, n_cells * L * 16),
+                    rb.array((n_cells, L), np.uint16, n_cells * L * 20),
+                    rb.array((n_cells, nw), np.uint8, n_cells * L * 22), W)
+        except BaseException as e:  # noqa: BLE001 - re-raised by take
+            self._err = e
+
+    def ready(self) -> bool:
+        """Whether take() would return at once (never blocks)."""
+        return not self._thread.is_alive()
+
+    def take(self) -> Rows16 | None:
+        """The rows once allocated (None without cells); the allocation's exception raised here."""
+        self._thread.join()
+        if self._err is not None:
+            raise self._err
+        return self._rows
+
+
 class CellProcessor:
     def __init__(self, config, output_dir, device: int = 0, devices: list[int] | None = None):
         self.config = config
@@ -118,7 +159,6 @@ class CellProcessor:
         self.coverage_opt: dict | None = None
         self.cluster_opt: dict | None = None
         self.neighbors_opt: dict | None = None
-        self._t_cov = self._t_var = 0.0
 
     # txt output on the device ----------------------------------------------
     def enable_device_txt(self, prefix, names: list[str]):
@@ -150,17 +190,14 @@ class CellProcessor:
                                  stabilize_variance=stabilize_variance,
                                  low_coverage_threshold=low_coverage_threshold, min_coverage=min_coverage)
 
-    def _call_variants(self, res: EngineResult, parts: list) -> float:
+    def _call_variants(self, res: EngineResult, parts: DeviceParts) -> None:
         """Pass 1 on every part (the devices concurrently), the host merge, pass 2, the
-        table, then the matrix of the passing variants, each part filling its own columns;
-        parts = [(engine, lo, hi)]. Returns the seconds spent."""
+        table, then the matrix of the passing variants, each part filling its own columns."""
         from ..analysis.variants import run_variants
         from ..file_io.writers import ref_alleles
 
-        t0 = time.perf_counter()
         pop, ref = self._population(res), ref_alleles(res.ref_tally)
-        res.variant_cells = None
-        cov = getattr(res, "coverage", None)
+        cov = res.coverage
         if self.coverage_opt is not None and cov is not None:
             # the vignette's order: the variants of the kept cells, with their own reference
             res.variant_cells = np.flatnonzero(cov.kept)
@@ -169,7 +206,6 @@ class CellProcessor:
                 ref = cov.ref_alleles
         vr = run_variants(parts, ref, cells=pop, **self.variants_opt)
         res.variants, res.allele_freq, res.variant_seconds = vr.table, vr.allele_freq, vr.seconds
-        return time.perf_counter() - t0
 
     def enable_clustering(self, clones: int | None = None):
         """Cluster the cells and the variants of the run's heteroplasmy matrix (mgp_hclust;
@@ -192,7 +228,7 @@ class CellProcessor:
 
         t0 = time.perf_counter()
         try:
-            res.clusters = cluster_heteroplasmy(getattr(res, "allele_freq", None), table=getattr(res, "variants", None),
+            res.clusters = cluster_heteroplasmy(res.allele_freq, table=res.variants,
                                                 clones=self.cluster_opt["clones"], device=self.devices[0])
         finally:
             self.last_timing["cluster"] = time.perf_counter() - t0
@@ -223,8 +259,8 @@ class CellProcessor:
 
         t0 = time.perf_counter()
         try:
-            res.neighbors = neighbor_graph(getattr(res, "allele_freq", None), table=getattr(res, "variants", None),
-                                           device=self.devices[0], **self.neighbors_opt)
+            res.neighbors = neighbor_graph(res.allele_freq, table=res.variants, device=self.devices[0],
+                                           **self.neighbors_opt)
         finally:
             self.last_timing["neighbors"] = time.perf_counter() - t0
         return res.neighbors
@@ -251,175 +287,47 @@ class CellProcessor:
                                  min_coverage_breadth=float(min_coverage_breadth),
                                  recompute_reference=bool(recompute_reference))
 
-    def _call_coverage(self, res: EngineResult, parts: list) -> float:
+    def _call_coverage(self, res: EngineResult, parts: DeviceParts) -> None:
         from ..analysis.coverage import run_coverage
 
-        t0 = time.perf_counter()
         res.coverage = run_coverage(parts, cells=self._population(res), **self.coverage_opt)
-        return time.perf_counter() - t0
-
-    def _call_analyses(self, res: EngineResult, parts: list) -> float:
-        """The coverage pass, then the variants (which use its kept cells), over parts =
-        [(engine, lo, hi)] while their contexts are open. Returns the seconds spent."""
-        self._t_cov = self._t_var = 0.0
-        if parts and self.coverage_opt is not None:
-            self._t_cov = self._call_coverage(res, parts)
-        if parts and self.variants_opt is not None:
-            self._t_var = self._call_variants(res, parts)
-        return self._t_cov + self._t_var
-
-    def _analysis_timing(self):
-        if self.coverage_opt is not None:
-            self.last_timing["coverage"] = self._t_cov
-        if self.variants_opt is not None:
-            self.last_timing["variants"] = self._t_var
 
     def _h5_device_on(self) -> bool:
         return self.h5_out is not None and os.environ.get("MGP_H5_DEVICE", "1") != "0"
-
-    def _write_h5(self, res: EngineResult, parts: list) -> float:
-        """The written cells' columns (hdf5_columns over the passing cells in first-seen
-        order), their chunks deflated on the devices: parts = [(engine, lo, hi)], each
-        engine holding the cells [lo, hi) as its 0..hi-lo. A column chunk whose cells lie
-        on one device is made there; one that spans two devices' cells (at most one per
-        boundary) is deflated on the host from the fetched rows. Returns the seconds spent."""
-        from concurrent.futures import ThreadPoolExecutor
-
-        from ..bam import h5_plane_tiles
-        from ..engine import H5_PLANES
-        from ..file_io.writers import hdf5_cell_of_col, hdf5_columns
-
-        t0 = time.perf_counter()
-        names = self.h5_out
-        sel, cols = hdf5_columns(names, names, cells_written(res))
-        if not (len(names) and sel.size):
-            return time.perf_counter() - t0
-        n, L = len(names), self.config.mito_length
-        coc = hdf5_cell_of_col(n, sel, cols)
-        chunks = (min(1000, L), min(100, n))
-        crow, ccol = chunks
-        nrc, ncc = -(-L // crow), -(-n // ccol)
-        los = np.array([lo for _, lo, _ in parts], np.int64)
-        his = np.array([hi for _, _, hi in parts], np.int64)
-        owner = np.zeros(ncc, np.int64)  # the part making each column chunk, -1: the host
-        for cc in range(ncc):
-            v = coc[cc * ccol:(cc + 1) * ccol]
-            v = v[v >= 0]
-            if v.size:
-                d = np.searchsorted(his, v, side="right")
-                owner[cc] = d[0] if np.all(d == d[0]) else -1
-        tiles = {p: [None] * (nrc * ncc) for p in H5_PLANES}
-        total = np.zeros((3, L), np.int64)
-
-        def runs(d):  # (c0, c1) runs of consecutive column chunks of part d
-            idx = np.flatnonzero(owner == d)
-            if not idx.size:
-                return []
-            cut = np.flatnonzero(np.diff(idx) > 1) + 1
-            return [(int(g[0]), int(g[-1]) + 1) for g in np.split(idx, cut)]
-
-        def one(d):
-            eng, lo, hi = parts[d]
-            local = np.where((coc >= lo) & (coc < hi), coc - lo, -1)
-            out = []
-            for c0, c1 in runs(d):
-                sums = {}
-                out.append((c0, c1, eng.h5_tiles(local, chunks, sums=sums, col_chunks=(c0, c1)), sums))
-            return out
-
-        if len(parts) > 1:
-            with ThreadPoolExecutor(len(parts)) as pool:
-                made = list(pool.map(one, range(len(parts))))
-        else:
-            made = [one(0)]
-        for got in made:
-            for c0, c1, tl, sums in got:
-                w = c1 - c0
-                for p in H5_PLANES:
-                    src = tl[p]
-                    for rc in range(nrc):
-                        tiles[p][rc * ncc + c0:rc * ncc + c1] = src[rc * w:(rc + 1) * w]
-                total += np.stack([sums["coverage"], sums["tn5_fwd"], sums["tn5_rev"]])
-        for cc in np.flatnonzero(owner < 0).tolist():  # chunks across a device boundary
-            sub = coc[cc * ccol:(cc + 1) * ccol]
-            made_h = (h5_plane_tiles(res.counts, sub, list(range(8)), chunks, level=4)
-                      + h5_plane_tiles(res.tn5, sub, [0, 1], chunks, level=4)
-                      + h5_plane_tiles(res.depth, sub, [0], chunks, level=4))
-            for p, lst in zip(H5_PLANES, made_h):
-                for rc in range(nrc):
-                    tiles[p][rc * ncc + cc] = lst[rc]
-            ok = sub[sub >= 0]
-            total[0] += np.minimum(res.depth[ok], 65535).astype(np.int64).sum(axis=0)
-            total[1] += np.minimum(res.tn5[ok, :, 0], 65535).astype(np.int64).sum(axis=0)
-            total[2] += np.minimum(res.tn5[ok, :, 1], 65535).astype(np.int64).sum(axis=0)
-        res.h5_tiles = (coc, chunks, tiles, {"coverage": total[0], "tn5_fwd": total[1], "tn5_rev": total[2]})
-        return time.perf_counter() - t0
 
     def _txt_device_on(self) -> bool:
         if self.txt_out is None or os.environ.get("MGP_TXT_DEVICE", "1") == "0":
             return False
         return os.environ.get("MGP_GZIP_LEVEL", "9") == "9"
 
-    def _write_txt(self, res: EngineResult, parts: list) -> float:
-        """The passing cells in first-seen order (processors.py:75's write order) through
-        mgp_txt_gz on their devices; parts = [(engine, lo, hi)], each engine holding the
-        cells [lo, hi) as its 0..hi-lo. With several devices each writes its own cells (in
-        the global order, TXT_CHUNK_CELLS per call, the devices concurrently) and the
-        members are interleaved back into the global order. Returns the seconds spent."""
-        t0 = time.perf_counter()
-        prefix, names = self.txt_out
-        written = cells_written(res)
-        files = [open(f"{prefix}.{f}.txt.gz", "ab") for f in TXT_FILES]
-        try:
-            if len(parts) == 1:
-                from concurrent.futures import ThreadPoolExecutor
+    def _write_txt(self, res: EngineResult, parts) -> None:
+        write_txt(res, DeviceParts(parts), *self.txt_out)
 
-                eng, lo, _ = parts[0]
+    def _write_h5(self, res: EngineResult, parts) -> None:
+        write_h5(res, DeviceParts(parts), self.h5_out, self.config.mito_length)
 
-                def put(mem):
-                    for f in range(5):
-                        files[f].write(memoryview(mem.file_part(f)))
-
-                # a chunk's members go to the files while the device makes the next chunk's
-                with ThreadPoolExecutor(1) as wr:
-                    pending = None
-                    for a in range(0, written.size, TXT_CHUNK_CELLS):
-                        chunk = written[a:a + TXT_CHUNK_CELLS]
-                        mem = eng.txt_gz(chunk - lo, [names[c] for c in chunk.tolist()])
-                        if pending is not None:
-                            pending.result()
-                        pending = wr.submit(put, mem)
-                    if pending is not None:
-                        pending.result()
-            else:
-                from concurrent.futures import ThreadPoolExecutor
-
-                his = np.array([hi for _, _, hi in parts], np.int64)
-                dev = np.searchsorted(his, written, side="right")  # each cell's part
-
-                def one(d):
-                    eng, lo, _ = parts[d]
-                    sel = written[dev == d]
-                    return [eng.txt_gz(ch - lo, [names[c] for c in ch.tolist()])
-                            for ch in (sel[a:a + TXT_CHUNK_CELLS] for a in range(0, sel.size, TXT_CHUNK_CELLS))]
-
-                with ThreadPoolExecutor(len(parts)) as pool:
-                    mems = list(pool.map(one, range(len(parts))))
-                rank = np.zeros(written.size, np.int64)  # a cell's index among its part's cells
-                for d in range(len(parts)):
-                    rank[dev == d] = np.arange(int((dev == d).sum()))
-                call, k_in = np.divmod(rank, TXT_CHUNK_CELLS)
-                order = list(zip(dev.tolist(), call.tolist(), k_in.tolist()))
-                for f in range(5):
-                    views = [[memoryview(m.file_part(f)) for m in ms] for ms in mems]
-                    offs = [[np.concatenate([[0], np.cumsum(m.member_bytes[f])]).tolist() for m in ms] for ms in mems]
-                    files[f].writelines(views[d][j][offs[d][j][k]:offs[d][j][k + 1]]
-                                        for d, j, k in order if offs[d][j][k + 1] > offs[d][j][k])
-        finally:
-            for fh in files:
-                fh.close()
-        res.txt_gz_cells = written
-        return time.perf_counter() - t0
+    def _after_run(self, res: EngineResult, parts: list, writers: bool = True) -> dict:
+        """What is made of the devices' rows while their contexts are open, over parts =
+        [(engine, lo, hi)] (shard.DeviceParts): the device txt writer, the device HDF5 writer,
+        the coverage pass, then the variants (which use its kept cells), each when enabled.
+        Returns the seconds of each under its last_timing key: txt_device and h5_device
+        always (writers=False: neither is run nor reported), coverage and variants when
+        enabled. A run without cells has no parts and makes nothing."""
+        steps = [("coverage", self.coverage_opt is not None, self._call_coverage),
+                 ("variants", self.variants_opt is not None, self._call_variants)]
+        seconds = {}
+        if writers:
+            steps = [("txt_device", self._txt_device_on(), self._write_txt),
+                     ("h5_device", self._h5_device_on(), self._write_h5)] + steps
+            seconds = {"txt_device": 0.0, "h5_device": 0.0}
+        live = DeviceParts(parts) if parts else None
+        for key, on, step in steps:
+            if on:
+                t0 = time.perf_counter()
+                if live is not None:
+                    step(res, live)
+                seconds[key] = time.perf_counter() - t0
+        return seconds
 
     # production path ------------------------------------------------------
     def run_soa(self, soa_batches, n_cells: int) -> EngineResult:
@@ -443,15 +351,12 @@ class CellProcessor:
             res = eng.fetch_compact()  # exact 16-bit rows: half the device-to-host bytes
             t3 = time.perf_counter()
             self.last_stats = eng.kernel_times()
-            t_txt = self._write_txt(res, [(eng, 0, n_cells)]) if self._txt_device_on() else 0.0
-            t_h5 = self._write_h5(res, [(eng, 0, n_cells)]) if self._h5_device_on() else 0.0
-            t_var = self._call_analyses(res, [(eng, 0, n_cells)])
+            tail = self._after_run(res, [(eng, 0, n_cells)])
         t4 = time.perf_counter()
         # where the engine leg goes (pipeline timings): context + allocation, H2D of
         # the batches + the run, D2H of the results, teardown
         self.last_timing = {"engine_open": t1 - t0, "engine_h2d_run": t2 - t1, "engine_d2h": t3 - t2,
-                            "engine_close": t4 - t3 - t_txt - t_h5 - t_var, "txt_device": t_txt, "h5_device": t_h5}
-        self._analysis_timing()
+                            "engine_close": t4 - t3 - sum(tail.values()), **tail}
         self.last_result = res
         return res
 
@@ -517,17 +422,6 @@ class CellProcessor:
             return ReadSoA(None, soa.bc, soa.tlen, soa.flag, soa.mapq, None, None, soa.payload)
         return soa
 
-    def _rows_target(self, n_cells: int, eng=None, windows: tuple[int, int] | None = None) -> Rows16 | None:
-        """Pinned 16-bit result rows for all cells (the rows target)."""
-        if n_cells <= 0:
-            return None
-        nw, W = windows if windows is not None else eng.windows()
-        L = self.config.mito_length
-        rb = PinnedBuffer(n_cells * L * 22 + n_cells * nw + 4096)
-        return Rows16(rb.array((n_cells, L, 8), np.uint16, 0), rb.array((n_cells, L, 2), np.uint16, n_cells * L * 16),
-                      rb.array((n_cells, L), np.uint16, n_cells * L * 20),
-                      rb.array((n_cells, nw), np.uint8, n_cells * L * 22), W)
-
     def run_stream(self, reader, n_cells: int, batch_reads: int | None = None,
                    rows_target: bool | None = None) -> EngineResult:
         """The production path, streamed (readers.py:84-93's one pass, overlapped with
@@ -556,32 +450,16 @@ class CellProcessor:
             ec.stream = True
             eng = Engine(ec, device=self.device)
             try:
-                # the rows target (GBs of pinned memory: ~0.25 s per GB to pin) is allocated
-                # on a thread while the first batches go in; the engine copies the rows of
-                # the windows piled before it is set when it is set (ABI 4)
-                rows, pending = None, None
-                if rows_target and n_cells > 0:
-                    box: dict = {}
-                    wins = eng.windows()
-
-                    def alloc():
-                        try:
-                            box["rows"] = self._rows_target(n_cells, windows=wins)
-                        except BaseException as e:  # noqa: BLE001 - re-raised below
-                            box["err"] = e
-
-                    pending = threading.Thread(target=alloc, name="mgp-rows-alloc", daemon=True)
-                    pending.start()
+                # the rows target is pinned while the first batches go in, and set when it is ready
+                target = _RowsTarget(n_cells, self.config.mito_length, eng.windows()) \
+                    if rows_target and n_cells > 0 else None
+                rows = None
 
                 def settle(wait: bool):
-                    nonlocal rows, pending
-                    if pending is None or (not wait and pending.is_alive()):
+                    nonlocal rows, target
+                    if target is None or not (wait or target.ready()):
                         return
-                    pending.join()
-                    pending = None
-                    if "err" in box:
-                        raise box["err"]
-                    rows = box.get("rows")
+                    rows, target = target.take(), None
                     if rows is not None:
                         eng.set_rows16_target(rows)
 
@@ -617,9 +495,7 @@ class CellProcessor:
                 t4 = time.perf_counter()
                 self.last_stats = eng.kernel_times()
                 _, last_streamed = eng.stream_info()
-                t_txt = self._write_txt(res, [(eng, 0, n_cells)]) if self._txt_device_on() else 0.0
-                t_h5 = self._write_h5(res, [(eng, 0, n_cells)]) if self._h5_device_on() else 0.0
-                t_var = self._call_analyses(res, [(eng, 0, n_cells)])
+                tail = self._after_run(res, [(eng, 0, n_cells)])
             finally:
                 free.put(None)
                 eng.close()
@@ -634,11 +510,10 @@ class CellProcessor:
         self.last_timing = {"stream_setup": t1 - t0, "stream_first_batch": times.get("first_batch", t1) - t0,
                             "stream_decode_end": dec_end - t0, "stream_push_end": t2 - t0,
                             "engine_tail": t3 - t2, "engine_fetch": t4 - t3,
-                            "engine_close": te - t4 - t_txt - t_h5 - t_var, "txt_device": t_txt, "h5_device": t_h5,
+                            "engine_close": te - t4 - sum(tail.values()), **tail,
                             "stream_batches": n_batches, "stream_batch_reads": times["cap_reads"],
                             "streamed_run": bool(last_streamed), "rows_target": rows is not None,
                             "h2d_bytes": int(h2d)}
-        self._analysis_timing()
         self.last_result = res
         return res
 
@@ -662,8 +537,6 @@ class CellProcessor:
 
         from ..bam import RoutePart, host_threads, route_batch
         from ..exceptions import ProcessingError
-        from ..shard import partition_cells
-
         devs = list(self.devices)
         D = len(devs)
         t0 = time.perf_counter()
@@ -707,41 +580,25 @@ class CellProcessor:
                 f = min(1.0, share[d] * 1.5 + 0.02)
                 return int(cap_r * f) + 65536, int(cap_p * f) + (1 << 20)
 
-            # the rows target (all cells, one pinned array) is pinned on a thread while the
-            # first batches go in; each device thread sets its view when it is ready (the
-            # engine copies the windows piled before, ABI 4)
-            rows_box: dict = {}
-            rows_ready = threading.Event()
-            if rows_target and parts:
-                wins = engines[parts[0][0]].windows()
-
-                def alloc():
-                    try:
-                        rows_box["rows"] = self._rows_target(n_cells, windows=wins)
-                    except BaseException as e:  # noqa: BLE001 - re-raised by the device threads
-                        rows_box["err"] = e
-                    rows_ready.set()
-
-                threading.Thread(target=alloc, name="mgp-rows-alloc", daemon=True).start()
+            # the rows target (all cells, one pinned array) is pinned while the first batches go
+            # in; each device thread sets its view of it when it is ready
+            target = _RowsTarget(n_cells, self.config.mito_length, engines[parts[0][0]].windows()) \
+                if rows_target and parts else None
 
             def work(d, lo, hi):
                 # the device's pinned batches (pinned here, beside the other devices'), then
                 # every routed batch pushed, its copy awaited, its arrays back to the ring
                 eng = engines[d]
-                view_set = not (rows_target and parts)
+                view_set = target is None
 
                 def set_view(wait: bool):
                     nonlocal view_set
-                    if view_set or (not wait and not rows_ready.is_set()):
+                    if view_set or not (wait or target.ready()):
                         return
-                    rows_ready.wait()
                     view_set = True
-                    if "err" in rows_box:
-                        raise rows_box["err"]
-                    r = rows_box["rows"]
+                    r = target.take()
                     if r is not None:
-                        eng.set_rows16_target(Rows16(r.counts[lo:hi], r.tn5[lo:hi], r.depth[lo:hi], r.wide[lo:hi],
-                                                     r.window_width))
+                        eng.set_rows16_target(_rows_slice(r, lo, hi))
 
                 try:
                     cr, cp = part_caps(d)
@@ -825,7 +682,7 @@ class CellProcessor:
                     workers[d].join()
             if errors:
                 raise errors[0]
-            rows = rows_box.get("rows")
+            rows = target.take() if target is not None else None
             t2 = time.perf_counter()
             L = self.config.mito_length
             # without a rows target: every device's exact 16-bit rows fetched into its cell
@@ -836,40 +693,24 @@ class CellProcessor:
                 src = Rows16(np.empty((n_cells, L, 8), np.uint16), np.empty((n_cells, L, 2), np.uint16),
                              np.empty((n_cells, L), np.uint16), np.zeros((n_cells, nw), np.uint8), W)
                 for d, lo, hi in parts:
-                    engines[d].fetch_rows16(lo=0, hi=hi - lo, out=Rows16(src.counts[lo:hi], src.tn5[lo:hi],
-                                                                        src.depth[lo:hi], src.wide[lo:hi], W))
+                    engines[d].fetch_rows16(lo=0, hi=hi - lo, out=_rows_slice(src, lo, hi))
             wide = src is None or bool(src.wide.any())
             res = EngineResult.alloc(n_cells, L, dense=wide)
-            st_sum = {k: 0 for k in ("filtered_reads", "n_barcodes", "duplicate_reads_with_length",
-                                     "duplicate_reads_position_only", "cells_passed")}
-            max_span, err = 0, 0
+            res.stats = merged_stats(st.records)  # (the decoder counts every read, routed or not)
             for d, lo, hi in parts:
                 r = engines[d].fetch(dense=wide)
-                for k in ("n_reads", "any_paired", "passed", "covered", "depth_sum", "depth_max", "median_lo",
-                          "median_hi"):
-                    getattr(res, k)[lo:hi] = getattr(r, k)
-                if wide:
-                    for k in ("counts", "tn5", "depth"):
-                        getattr(res, k)[lo:hi] = getattr(r, k)
+                copy_part(res, r, lo, hi, dense=wide)
                 res.ref_tally += r.ref_tally
-                for k in st_sum:
-                    st_sum[k] += int(r.stats[k])
-                max_span = max(max_span, int(r.stats["max_span"]))
-                err |= int(r.stats["error_bits"])
+                res.stats["error_bits"] |= int(r.stats["error_bits"])
             # each cell's first read in the BAM (the router's index over the whole stream)
             res.first_read[:] = first_seen[:n_cells]
             if np.any((res.n_reads > 0) != (res.first_read != 0xFFFFFFFF)):
                 raise ProcessingError("routed reads and per-cell read counts disagree")
             if not wide:
                 res.counts, res.tn5, res.depth = src.counts, src.tn5, src.depth
-            res.stats = {"total_reads": int(st.records), **st_sum, "max_span": max_span, "error_bits": err}
             t3 = time.perf_counter()
             self.last_stats = engines[parts[0][0]].kernel_times() if parts else {}
-            t_txt = self._write_txt(res, [(engines[d], lo, hi) for d, lo, hi in parts]) \
-                if parts and self._txt_device_on() else 0.0
-            t_h5 = self._write_h5(res, [(engines[d], lo, hi) for d, lo, hi in parts]) \
-                if parts and self._h5_device_on() else 0.0
-            t_var = self._call_analyses(res, [(engines[d], lo, hi) for d, lo, hi in parts])
+            tail = self._after_run(res, [(engines[d], lo, hi) for d, lo, hi in parts])
         finally:
             free.put(None)
             for eng in engines.values():
@@ -880,13 +721,12 @@ class CellProcessor:
         te = time.perf_counter()
         self.last_timing = {"stream_setup": t1 - t0, "stream_first_batch": times.get("first_batch", t1) - t0,
                             "stream_decode_end": times.get("decode_end", t2) - t0, "stream_push_end": t2 - t0,
-                            "engine_tail": 0.0, "engine_fetch": t3 - t2, "engine_close": te - t3 - t_txt - t_h5 - t_var,
-                            "txt_device": t_txt, "h5_device": t_h5,
+                            "engine_tail": 0.0, "engine_fetch": t3 - t2,
+                            "engine_close": te - t3 - sum(tail.values()), **tail,
                             "stream_batches": n_batches, "stream_batch_reads": times["cap_reads"],
                             "stream_devices": len(parts), "rows_target": rows is not None, "route_s": t_route,
                             "h2d_bytes": int(sum(link_bytes.values())),
                             "cell_bounds": [lo for _, lo, _ in parts] + ([parts[-1][2]] if parts else [])}
-        self._analysis_timing()
         self.last_result = res
         return res
 
@@ -896,14 +736,15 @@ class CellProcessor:
         cells and tallies summed on the host."""
         from concurrent.futures import ThreadPoolExecutor
 
-        from ..shard import merge_results, partition_cells, reads_per_cell, shard_soa
         from ..synth import concat_soa
 
         soa = soa_batches[0] if len(soa_batches) == 1 else concat_soa(soa_batches)
         b = partition_cells(reads_per_cell(soa, n_cells), len(self.devices))
         shards = [(int(lo), int(hi)) + shard_soa(soa, int(lo), int(hi)) for lo, hi in zip(b[:-1], b[1:])]
 
-        engines: list = [None] * len(self.devices)  # open until the coverage and variant passes have read their rows
+        # (the engines stay open only for the coverage and variant passes to read their rows)
+        keep_open = self.variants_opt is not None or self.coverage_opt is not None
+        engines: list = [None] * len(self.devices)
 
         def one(i):
             lo, hi, sub, idx = shards[i]
@@ -915,18 +756,15 @@ class CellProcessor:
                 eng.run()
                 return eng.fetch_compact(), lo, hi, idx
             finally:
-                if self.variants_opt is None and self.coverage_opt is None:
+                if not keep_open:
                     eng.close()
 
         try:
             with ThreadPoolExecutor(len(self.devices)) as ex:
                 parts = list(ex.map(one, range(len(self.devices))))
             res = merge_results(parts, n_cells, soa.n)
-            if self.variants_opt is not None or self.coverage_opt is not None:
-                live = [(engines[i], lo, hi) for i, (_, lo, hi, _) in enumerate(parts) if hi > lo]
-                self._call_analyses(res, live)
-                self.last_timing = {}
-                self._analysis_timing()
+            live = [(engines[i], lo, hi) for i, (_, lo, hi, _) in enumerate(parts) if hi > lo]
+            self.last_timing = self._after_run(res, live, writers=False)  # (this path has no device writers)
         finally:
             for eng in engines:
                 if eng is not None:
@@ -978,7 +816,3 @@ class CellProcessor:
         logger.info(f"Processing {n_cells} cells at an average of {avg:.0f} reads/cell")
         return self.process_cells_direct(reads_by_barcode, incremental_writer)
 
-
-def cells_written(res: EngineResult) -> np.ndarray:
-    order = res.cell_order()
-    return order[res.passed[order].astype(bool)]

@@ -16,7 +16,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import EngineResult
+from .engine import VARIANT_MAX_CELLS, Engine, EngineResult
+from .exceptions import InvalidInputError
 from .synth import ReadSoA
 
 
@@ -107,8 +108,78 @@ def shard_soa(soa: ReadSoA, lo: int, hi: int, rec_align: int = 64, paired: bool 
     return out, idx
 
 
-_STAT_SUM = ("filtered_reads", "n_barcodes", "duplicate_reads_with_length", "duplicate_reads_position_only",
-             "cells_passed")
+class DeviceParts(list):
+    """The device parts of a run: the list [(engine, lo, hi)], each engine holding the cells
+    [lo, hi) of the run as its 0..hi-lo, the ranges ascending and disjoint. The one place that
+    maps global cell indices onto them."""
+
+    def __init__(self, source):
+        """`source`: an Engine after run() (one part with all its cells) or parts [(engine, lo, hi)]."""
+        if isinstance(source, Engine):
+            source = [(source, 0, source.cfg.n_cells)]
+        super().__init__((e, int(lo), int(hi)) for e, lo, hi in source)
+        if not self:
+            raise InvalidInputError("identify_variants: no device parts")
+        self._his = np.array([hi for _, _, hi in self], np.int64)
+
+    def all_cells(self) -> np.ndarray:
+        """Every cell of every part, in part order."""
+        return np.concatenate([np.arange(lo, hi, dtype=np.int64) for _, lo, hi in self])
+
+    def owner(self, cells) -> np.ndarray:
+        """The part holding each (non-negative) cell; len(self) for a cell past the last part."""
+        return np.searchsorted(self._his, cells, side="right")
+
+    def local(self, d: int, cells) -> np.ndarray:
+        """The cells as part d's own indices, -1 where a cell is not part d's."""
+        _, lo, hi = self[d]
+        cells = np.asarray(cells)
+        return np.where((cells >= lo) & (cells < hi), cells - lo, -1)
+
+    def split(self, cells: np.ndarray, max_cells: int = VARIANT_MAX_CELLS) -> list[list[tuple]]:
+        """A population (global cell indices, -1: an all-zero row) split over the parts: per
+        part, the indices into `cells` it owns (in order) and their part-local indices (int32),
+        in calls of at most max_cells cells (one mgp_variant_* / mgp_*_coverage call's bound). The
+        all-zero rows go with the first part."""
+        calls = []
+        for d in range(len(self)):
+            local = self.local(d, cells)
+            idx = np.flatnonzero((local >= 0) | (cells < 0) if d == 0 else local >= 0)
+            local = local[idx].astype(np.int32)
+            calls.append([(idx[a:a + max_cells], local[a:a + max_cells]) for a in range(0, idx.size, max_cells)])
+        if sum(ix.size for ch in calls for ix, _ in ch) != cells.size:
+            raise InvalidInputError("identify_variants: a cell of the population is on no device part")
+        return calls
+
+    def map(self, fn) -> list:
+        """fn(d) for every part, in part order, the devices concurrently (ctypes releases the GIL)."""
+        if len(self) == 1:
+            return [fn(0)]
+        from concurrent.futures import ThreadPoolExecutor
+
+        with ThreadPoolExecutor(len(self)) as pool:
+            return list(pool.map(fn, range(len(self))))
+
+
+PER_CELL = ("n_reads", "any_paired", "passed", "covered", "depth_sum", "depth_max", "median_lo", "median_hi")
+STAT_SUM = ("filtered_reads", "n_barcodes", "duplicate_reads_with_length", "duplicate_reads_position_only",
+            "cells_passed")
+
+
+def merged_stats(total_reads: int) -> dict:
+    """The stats of a merged result before any part is copied in."""
+    return {"total_reads": int(total_reads), **dict.fromkeys(STAT_SUM, 0), "max_span": 0, "error_bits": 0}
+
+
+def copy_part(out: EngineResult, res: EngineResult, lo: int, hi: int, dense: bool) -> None:
+    """A part's per-cell fields (dense: its u32 rows too) into the cells [lo, hi) of `out`, and its
+    counters into out.stats (merged_stats): STAT_SUM added, max_span by max. first_read, the
+    tally and error_bits differ between the merges and stay with them."""
+    for k in PER_CELL + (("counts", "tn5", "depth") if dense else ()):
+        getattr(out, k)[lo:hi] = getattr(res, k)
+    for k in STAT_SUM:
+        out.stats[k] += int(res.stats.get(k, 0))
+    out.stats["max_span"] = max(out.stats["max_span"], int(res.stats.get("max_span", 0)))
 
 
 def merge_results(parts: list[tuple[EngineResult, int, int, np.ndarray]], n_cells: int, total_reads: int,
@@ -126,13 +197,9 @@ def merge_results(parts: list[tuple[EngineResult, int, int, np.ndarray]], n_cell
     dense = r0.counts is not None
     L = r0.ref_tally.shape[0]
     out = EngineResult.alloc(n_cells, L, dense=dense)
+    out.stats = merged_stats(total_reads)  # (error_bits stays 0)
     for res, lo, hi, idx in parts:
-        for k in ("counts", "tn5", "depth"):
-            if dense:
-                getattr(out, k)[lo:hi] = getattr(res, k)
-        for k in ("n_reads", "any_paired", "passed", "covered", "depth_sum", "depth_max", "median_lo",
-                  "median_hi"):
-            getattr(out, k)[lo:hi] = getattr(res, k)
+        copy_part(out, res, lo, hi, dense)
         fr = res.first_read.astype(np.int64)
         has = res.n_reads > 0
         mapped = np.full(hi - lo, np.iinfo(np.uint32).max, np.int64)
@@ -142,9 +209,5 @@ def merge_results(parts: list[tuple[EngineResult, int, int, np.ndarray]], n_cell
             out.ref_tally += res.ref_tally
     if tally_reduced:
         out.ref_tally[:] = r0.ref_tally
-    st = {k: sum(int(p[0].stats.get(k, 0)) for p in parts) for k in _STAT_SUM}
-    st["total_reads"] = int(total_reads)
-    st["max_span"] = max(int(p[0].stats.get("max_span", 0)) for p in parts)
-    st["error_bits"] = 0
-    out.stats = st
     return out
+

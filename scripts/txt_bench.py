@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=2)
     args = ap.parse_args()
     from mgatk2_amd.engine import Engine, EngineConfig
-    from mgatk2_amd.processing.processors import cells_written
+    from mgatk2_amd.processing.device_writers import cells_written
     from mgatk2_amd.synth import barcode_names, cell_cdf, ref_codes
 
     seed = 20251015 + 4

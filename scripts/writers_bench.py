@@ -53,7 +53,7 @@ def fake_result(n_cells: int, L: int, depth: float, seed: int, dtype=np.uint16):
         counts=counts, depth=dep, tn5=tn5, covered=covered, depth_sum=dsum,
         depth_max=dep.max(1).astype(np.int64), median_lo=srt[:, (L - 1) // 2].astype(np.int64),
         median_hi=srt[:, L // 2].astype(np.int64), n_reads=(dsum // 50).astype(np.int64),
-        any_paired=np.ones(n_cells, bool),
+        any_paired=np.ones(n_cells, bool), txt_gz_cells=None, h5_tiles=None,  # (nothing written on a device)
     )
 
 

@@ -724,18 +724,21 @@ class _OracleEngine:
         pass
 
 
+class HostBuf:
+    """engine.PinnedBuffer in plain host memory."""
+
+    def __init__(self, nbytes):
+        self.buf = np.zeros(int(nbytes) + 64, np.uint8)
+
+    def array(self, shape, dtype, offset=0):
+        dt = np.dtype(dtype)
+        shape = (int(shape),) if np.ndim(shape) == 0 else tuple(int(x) for x in shape)
+        n = int(np.prod(shape)) * dt.itemsize
+        return self.buf[offset:offset + n].view(dt).reshape(shape)
+
+
 def _stand_in_devices(monkeypatch, oracle_lib):
     from mgatk2_amd.processing import processors
-
-    class HostBuf:
-        def __init__(self, nbytes):
-            self.buf = np.zeros(int(nbytes) + 64, np.uint8)
-
-        def array(self, shape, dtype, offset=0):
-            dt = np.dtype(dtype)
-            shape = (int(shape),) if np.ndim(shape) == 0 else tuple(int(x) for x in shape)
-            n = int(np.prod(shape)) * dt.itemsize
-            return self.buf[offset:offset + n].view(dt).reshape(shape)
 
     _OracleEngine.oracle = oracle_lib
     _OracleEngine.pushed = []
@@ -747,7 +750,7 @@ def _stand_in_devices(monkeypatch, oracle_lib):
 def test_stream_sharded_hdf5_host(n_dev, tmp_path, oracle_lib, monkeypatch):
     """The streamed multi-device path with HDF5 output: each column chunk of the datasets
     deflated by the (stand-in) device holding its cells, the chunks across a device
-    boundary on the host (CellProcessor._write_h5); the files equal the reference's."""
+    boundary on the host (device_writers.write_h5); the files equal the reference's."""
     _stand_in_devices(monkeypatch, oracle_lib)
     monkeypatch.setenv("MGP_STREAM_BATCH", "997")
     from mgatk2_amd.pipeline import run_pipeline
@@ -770,8 +773,8 @@ def test_stream_sharded_hdf5_host(n_dev, tmp_path, oracle_lib, monkeypatch):
 
 
 def test_write_h5_partition(tmp_path, oracle_lib):
-    """CellProcessor._write_h5 over 3 stand-in devices holding cell ranges that do not
-    fall on 100-column chunk edges, columns shuffled and repeated: every chunk equals
+    """CellProcessor._write_h5 (device_writers.write_h5) over 3 stand-in devices holding cell
+    ranges that do not fall on 100-column chunk edges, columns shuffled and repeated: every chunk equals
     the host deflate's of the same plane, and the report's column sums are the planes'."""
     import zlib
 
@@ -827,24 +830,9 @@ def test_stream_sharded_routing_host(n_dev, rows, layout, tmp_path, oracle_lib, 
     monkeypatch.setenv("MGP_ROWS_TARGET", rows)
     monkeypatch.setenv("MGP_RECORDS", layout[:2])
     monkeypatch.setenv("MGP_PLACEMENT", "paired" if layout.endswith("paired") else "device")
-    from mgatk2_amd.engine import PinnedBuffer  # noqa: F401 - (host memory in this stand-in)
-    from mgatk2_amd.processing import processors
     from mgatk2_amd.pipeline import run_pipeline
 
-    class HostBuf:
-        def __init__(self, nbytes):
-            self.buf = np.zeros(int(nbytes) + 64, np.uint8)
-
-        def array(self, shape, dtype, offset=0):
-            dt = np.dtype(dtype)
-            shape = (int(shape),) if np.ndim(shape) == 0 else tuple(int(x) for x in shape)
-            n = int(np.prod(shape)) * dt.itemsize
-            return self.buf[offset:offset + n].view(dt).reshape(shape)
-
-    _OracleEngine.oracle = oracle_lib
-    _OracleEngine.pushed = []
-    monkeypatch.setattr(processors, "Engine", _OracleEngine)
-    monkeypatch.setattr(processors, "PinnedBuffer", HostBuf)
+    _stand_in_devices(monkeypatch, oracle_lib)
     monkeypatch.setenv("MGP_STREAM_BATCH", "997")
     g = Golden("synth_run")
     p = g.params
