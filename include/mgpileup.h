@@ -69,7 +69,8 @@ extern "C" {
                                  mgp_pair_dist, mgp_hclust_dist, mgp_hclust (clustering by
                                  heteroplasmy on the device),
                                  mgp_knn, mgp_snn (the cells' kNN and SNN graphs by heteroplasmy
-                                 on the device) */
+                                 on the device),
+                                 mgp_bgzf_inflate, mgp_inflater_* (BGZF inflate on the device) */
 
 /* ---- return codes (0 = success) ------------------------------------------ */
 #define MGP_OK               0
@@ -840,6 +841,43 @@ int  mgp_synth_generate(mgp_ctx *ctx, const mgp_synth_params *p);
 int  mgp_download_inputs(mgp_ctx *ctx, int32_t *start, int32_t *bc, int32_t *tlen,
                          uint16_t *flag, uint8_t *mapq, uint32_t *span,
                          uint64_t *rec_off, uint8_t *payload);
+
+/* ---- BGZF inflate on the device ---------------------------
+ * Replaces nothing in the reference (pysam / htslib inflate BGZF on the host). Block i of a
+ * call is the raw deflate stream (RFC 1951: stored, fixed and dynamic blocks, any number of
+ * them) src[coff[i], coff[i] + clen[i]) and inflates to exactly isize[i] <= 65,536 bytes at
+ * out[out_off[i], ...): one wave per block, CRC32 left to the caller. status[i]: 0 ok;
+ * 1 invalid stream (reserved block type, stored LEN/NLEN mismatch, a bad or over-subscribed
+ * code-length set, a repeat with nothing to repeat or past the count, no end-of-block code,
+ * literal/length symbol 286/287, distance symbol 30/31, a distance before the start of the
+ * output); 2 the stream gives more or fewer than isize bytes, or the input ends before the
+ * final block does. Bytes after the final block are ignored. A block with a non-zero status
+ * leaves out untouched outside its own range, and the call still returns 0: the statuses
+ * are the result.
+ * Refused before any allocation or launch (MGP_E_INVALID): null pointers, negative counts,
+ * isize[i] > 65,536, a compressed range outside src, an output range outside out, output
+ * ranges not sorted or overlapping. n_blocks == 0 launches nothing. */
+int  mgp_bgzf_inflate(int device, const uint8_t *src, int64_t src_bytes, int64_t n_blocks,
+                      const uint64_t *coff, const uint32_t *clen, const uint32_t *isize, const uint64_t *out_off,
+                      uint8_t *out, int64_t out_bytes, int32_t *status /* [n_blocks] */);
+/* The same with device buffers for max_src_bytes / max_out_bytes, one stream and pinned
+ * staging kept across calls (the ingest's form). A failed create leaves nothing allocated. */
+typedef struct mgp_inflater mgp_inflater;
+int  mgp_inflater_create(int device, int64_t max_src_bytes, int64_t max_out_bytes, mgp_inflater **out);
+void mgp_inflater_destroy(mgp_inflater *inflater);
+/* One call: H2D of src, the kernel, D2H of the blocks' ranges, and the wait, on the
+ * inflater's stream; selects the inflater's device on the calling thread. More bytes than
+ * the inflater was created for: MGP_E_INVALID. The signature is mgp_bam_inflate_fn's
+ * (include/mgpileup_host.h): `inflater` is the hook's ctx, mgp_last_error its message. */
+int  mgp_inflater_run(void *inflater, const uint8_t *src, int64_t src_bytes, int64_t n_blocks,
+                      const uint64_t *coff, const uint32_t *clen, const uint32_t *isize, const uint64_t *out_off,
+                      uint8_t *out, int64_t out_bytes, int32_t *status);
+/* Device times of the inflater's calls so far, summed (HIP events on its stream): ms3 = H2D,
+ * kernel, D2H in milliseconds; calls and blocks (either may be NULL) count them. */
+int  mgp_inflater_times(mgp_inflater *inflater, double *ms3, int64_t *calls, int64_t *blocks);
+/* mgp_host_alloc / mgp_host_free in the shape of the hook's allocators (NULL on failure). */
+void *mgp_inflater_host_alloc(int64_t bytes);
+void  mgp_inflater_host_release(void *p);
 
 #ifdef __cplusplus
 }

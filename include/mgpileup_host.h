@@ -77,6 +77,33 @@ int  mgp_bam_set_pack32(mgp_bam *bam, int on, int min_baseq, int min_dist);
  * MGP_PLACE_PAIRED: see mgp_place_records below). */
 int  mgp_bam_set_placement(mgp_bam *bam, int mode);
 
+/* BGZF inflate by the caller (the device inflate of libmgpileup.so, include/mgpileup.h
+ * mgp_inflater_run; this library stays free of any GPU dependency). With an inflater set,
+ * every chunk of whole BGZF blocks the prefetch thread has read goes through one `run`
+ * call, on that thread: block i is the raw deflate stream src[coff[i], coff[i] + clen[i])
+ * (past the block's 12 + XLEN header, before its 8-byte trailer) and inflates to isize[i]
+ * bytes at out[out_off[i], ...), at most 16 MiB of src and 256 MiB of out in a call;
+ * status[i] = 0 when it did. The pool then checks every
+ * status and the CRC32 of every block against its trailer: a non-zero status or a mismatch
+ * is the "BGZF inflate/CRC error" of the host inflate, a non-zero return of `run` an error
+ * that carries `message()` (may be NULL). Nothing falls back to the host inflate. With
+ * alloc / release (both or neither; NULL: plain memory) the chunks' inflated and compressed
+ * buffers come from them, e.g. pinned memory. Applies to the reads begun after the call
+ * (mgp_bam_read_ref, mgp_bam_stream_open, mgp_bam_find_tag, mgp_bam_count_tag); the header
+ * parse of mgp_bam_open is the host's. NULL: back to the host inflate. `*inf` is copied;
+ * what ctx points to must outlive the bam's reads. */
+typedef int (*mgp_bam_inflate_fn)(void *ctx, const uint8_t *src, int64_t src_bytes, int64_t n_blocks,
+                                  const uint64_t *coff, const uint32_t *clen, const uint32_t *isize,
+                                  const uint64_t *out_off, uint8_t *out, int64_t out_bytes, int32_t *status);
+typedef struct mgp_bam_inflater {
+    mgp_bam_inflate_fn run;
+    void *ctx;
+    void *(*alloc)(int64_t bytes);
+    void (*release)(void *p);
+    const char *(*message)(void);   /* the message of a failed run, on the calling thread */
+} mgp_bam_inflater;
+int  mgp_bam_set_inflater(mgp_bam *bam, const mgp_bam_inflater *inf);
+
 /* Decode every record of reference `tid` (fetch(contig) order) into `out`.
  * Records are placed at multiples of `rec_align` bytes (16..4096, power of 2). */
 int  mgp_bam_read_ref(mgp_bam *bam, int tid, int rec_align, mgp_bam_batch *out);

@@ -56,6 +56,13 @@ class mgp_route_part(C.Structure):
 _hlib = None
 
 
+class mgp_bam_inflater(C.Structure):
+    """include/mgpileup_host.h: the BGZF inflate hook (addresses of C functions)."""
+
+    _fields_ = [("run", C.c_void_p), ("ctx", C.c_void_p), ("alloc", C.c_void_p), ("release", C.c_void_p),
+                ("message", C.c_void_p)]
+
+
 def cgroup_cpu_quota() -> int | None:
     """CPUs the process's cgroup may use (cgroup v2 cpu.max, else v1
     cpu.cfs_quota_us / cpu.cfs_period_us), rounded up; None when unlimited or unknown."""
@@ -180,6 +187,8 @@ def host_library() -> C.CDLL:
         lib.mgp_route_batch.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, C.c_int64, vp,
                                         C.POINTER(mgp_route_part), C.c_int]
         lib.mgp_route_batch.restype = C.c_int
+        lib.mgp_bam_set_inflater.argtypes = [vp, C.POINTER(mgp_bam_inflater)]
+        lib.mgp_bam_set_inflater.restype = C.c_int
         _hlib = lib
     return _hlib
 
@@ -276,6 +285,10 @@ class BamFile:
         if getattr(self, "_h", None):
             self.lib.mgp_bam_close(self._h)
             self._h = None
+        inf = getattr(self, "_inflater", None)
+        if inf is not None:  # (after the bam: no read of it is left to call the hook)
+            inf.close()
+            self._inflater = None
 
     def __enter__(self):
         return self
@@ -291,6 +304,37 @@ class BamFile:
 
     def tid(self, contig: str) -> int:
         return self.references.index(contig)
+
+    def set_device_inflate(self, device: int | None, pinned: bool = True) -> None:
+        """BGZF blocks inflated on `device` (mgp_inflater_run of libmgpileup.so, one call per
+        chunk on the prefetch thread; CRC32 stays on the host pool) for every read begun after
+        the call; None: back to the host inflate. The hook is the C function's address: no
+        Python runs per chunk. pinned: the chunk buffers come from mgp_host_alloc, so both
+        copies are DMA. A device fault is an error, never a fallback to the host inflate."""
+        if device is None:
+            if self.lib.mgp_bam_set_inflater(self._h, None) != 0:
+                raise ProcessingError(_err())
+            old, self._inflater = getattr(self, "_inflater", None), None
+            if old is not None:
+                old.close()
+            return
+        from . import engine
+
+        elib = engine.load_library()
+        # a chunk is at most 16 MiB of compressed blocks inflating to at most 256 MiB (the
+        # bounds of one `run` call, include/mgpileup_host.h)
+        inf = engine.Inflater(int(device), max_src_bytes=16 << 20, max_out_bytes=256 << 20)
+        addr = lambda f: C.cast(f, C.c_void_p).value
+        hook = mgp_bam_inflater(addr(elib.mgp_inflater_run), inf.handle,
+                                addr(elib.mgp_inflater_host_alloc) if pinned else None,
+                                addr(elib.mgp_inflater_host_release) if pinned else None,
+                                addr(elib.mgp_last_error))
+        if self.lib.mgp_bam_set_inflater(self._h, C.byref(hook)) != 0:
+            inf.close()
+            raise ProcessingError(_err())
+        old, self._inflater = getattr(self, "_inflater", None), inf  # (lives as long as the BamFile)
+        if old is not None:
+            old.close()
 
     def read_soa(self, contig: str, barcodes: list[str], tag: str = "CB", rec_align: int = 64,
                  bulk_cell: int = -1, pack: bool = True, paired: bool | None = None,

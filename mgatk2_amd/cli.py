@@ -72,6 +72,9 @@ def _variant_options(f):
         click.option("--snn-prune", default=None, type=click.FloatRange(min=0.0, max=1.0), metavar="P",
                      help="Drop SNN edges of Jaccard weight below P (Seurat's prune.SNN)  [default: 1/15]; "
                           "needs --neighbors"),
+        click.option("--device-inflate", "device_inflate", is_flag=True,
+                     help="Inflate the BAM's BGZF blocks on the device (the first of --devices); CRC32 stays on "
+                          "the host. Off by default"),
     ]
     for o in reversed(opts):
         f = o(f)
@@ -81,13 +84,13 @@ def _variant_options(f):
 def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
                   variant_low_coverage, variant_min_coverage, coverage_stats=False, cell_min_mean_coverage=0.0,
                   cell_min_coverage_breadth=0.0, recompute_reference=False, cluster=False, clones=None, neighbors=None,
-                  snn_prune=None) -> dict:
+                  snn_prune=None, device_inflate=False) -> dict:
     """The options run_pipeline gets beyond the reference's, each only when asked for: the
     variant options with --variants; the four coverage options with --coverage-stats,
     otherwise the filter thresholds and --recompute-reference that were given; --cluster and
     --clones when given (--cluster needs --variants, --clones needs --cluster: a usage error);
     --neighbors and --snn-prune when given (--neighbors needs --variants, --snn-prune needs
-    --neighbors: a usage error)."""
+    --neighbors: a usage error); --device-inflate when given."""
     if neighbors is not None and not call_variants:
         raise click.UsageError("--neighbors requires --variants")
     if snn_prune is not None and neighbors is None:
@@ -119,6 +122,8 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
         out.update(neighbors=int(neighbors))
         if snn_prune is not None:
             out.update(snn_prune=float(snn_prune))
+    if device_inflate:
+        out.update(device_inflate=True)
     return out
 
 
@@ -332,6 +337,8 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
         if variant_args and variant_args.get("neighbors") is not None:
             logger.info("  Neighbour graph:        k.param %s, SNN prune %s", variant_args["neighbors"],
                         variant_args.get("snn_prune", "1/15"))
+        if variant_args and variant_args.get("device_inflate"):
+            logger.info("  BGZF inflate:           on the device")
         if dry_run:
             return 0
         if report_title is None:

@@ -84,6 +84,8 @@ class PipelineConfig:
         barcode_tag: str = "CB",
         mito_chr: str = "chrM",
         mito_length: int = 16569,
+        device_inflate: bool = False,
+        inflate_device: int = 0,
         **kwargs,
     ):
         self.quality = QualityThresholds(min_baseq=min_baseq, min_mapq=min_mapq, max_strand_bias=max_strand_bias)
@@ -99,6 +101,10 @@ class PipelineConfig:
         self.barcode_tag = barcode_tag
         self.mito_chr = mito_chr
         self.mito_length = mito_length
+        # BGZF blocks inflated on the device `inflate_device` (BamFile.set_device_inflate); off:
+        # the host pool's inflate
+        self.device_inflate = bool(device_inflate)
+        self.inflate_device = int(inflate_device)
 
     @property
     def dedup_mode(self) -> str:

@@ -159,6 +159,7 @@ struct mgp_bam {
     int pack32_minq = 0;
     int pack32_dist = 5;
     int placement = MGP_PLACE_DENSE;  // payload placement (mgp_place_records)
+    mgp_bam_inflater inflater{nullptr, nullptr, nullptr, nullptr, nullptr};  // run == NULL: the host inflate
 };
 
 namespace {
@@ -249,12 +250,72 @@ class Worker {
     std::thread th_;
 };
 
+// Bytes from the inflater's allocator (mgp_bam_inflater.alloc / .release: pinned memory the
+// device copies from and to) or, without one, plain memory; freed by what allocated them.
+class HostBuf {
+  public:
+    HostBuf() = default;
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+    ~HostBuf() { reset(); }
+    uint8_t* get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset() {
+        if (p_) {
+            if (rel_) rel_(p_);
+            else delete[] p_;
+        }
+        p_ = nullptr;
+    }
+    // a new buffer of n bytes (the old one's bytes are not kept); false: out of memory
+    bool alloc(size_t n, const mgp_bam_inflater& inf) {
+        reset();
+        if (inf.alloc && inf.release) {
+            p_ = static_cast<uint8_t*>(inf.alloc((int64_t)n));
+            rel_ = inf.release;
+        } else {
+            p_ = new (std::nothrow) uint8_t[n];
+            rel_ = nullptr;
+        }
+        return p_ != nullptr;
+    }
+    void swap(HostBuf& o) {
+        std::swap(p_, o.p_);
+        std::swap(rel_, o.rel_);
+    }
+
+  private:
+    uint8_t* p_ = nullptr;
+    void (*rel_)(void*) = nullptr;
+};
+
+// The compressed bytes of a chunk: a vector, or with the inflater's allocator a HostBuf.
+struct RawBytes {
+    std::vector<uint8_t> v;
+    HostBuf h;
+    size_t hcap = 0;
+    bool resize(size_t n, const mgp_bam_inflater& inf) {
+        if (!(inf.alloc && inf.release)) return v.resize(n), true;
+        if (n <= hcap && h) return true;
+        hcap = 0;
+        if (!h.alloc(n + (n >> 3), inf)) return false;
+        hcap = n + (n >> 3);
+        return true;
+    }
+    uint8_t* data() { return h ? h.get() : v.data(); }
+    void swap(RawBytes& o) {
+        v.swap(o.v);
+        h.swap(o.h);
+        std::swap(hcap, o.hcap);
+    }
+};
+
 // An inflated chunk of the BGZF stream: the bytes of consecutive whole blocks at
 // mem + kHead (the room in front takes the partial record the consumer carries over
 // from the chunk before).
 constexpr size_t kHead = 1u << 20;
 struct Chunk {
-    std::unique_ptr<uint8_t[]> mem;
+    HostBuf mem;
     size_t cap = 0;
     size_t n = 0;       // inflated bytes at mem + kHead
     bool last = false;  // the end of the file follows
@@ -276,8 +337,8 @@ class Prefetch {
     // the first record starting walk_from bytes into the first chunk (the stream decode's
     // serial boundary walk, off the consumer's thread)
     Prefetch(mgp_bam* bam, uint64_t coff, int64_t walk_from = -1)
-        : bam_(bam), coff_(coff), pool_(std::max(1, bam->n_threads)), walking_(walk_from >= 0),
-          wnext_(walk_from) {
+        : bam_(bam), coff_(coff), inf_(bam->inflater), pool_(std::max(1, bam->n_threads)),
+          walking_(walk_from >= 0), wnext_(walk_from) {
         th_ = std::thread([this] { run(); });
     }
     ~Prefetch() {
@@ -316,6 +377,7 @@ class Prefetch {
 
   private:
     static constexpr size_t kMaxBatch = 16u << 20;
+    static constexpr size_t kMaxInflated = 256u << 20;  // of one chunk handed to an inflater
     static constexpr size_t kAhead = 2;
     void set_fail(const std::string& m) {
         std::lock_guard<std::mutex> g(mu_);
@@ -373,7 +435,7 @@ class Prefetch {
             ~Settle() { p->settle_walk(); }
         } settle{this};
         size_t want_c = 64u << 10;
-        std::vector<uint8_t> raw;
+        RawBytes raw;
         std::vector<Block> blocks;
         bool last = false;
         while (!last) {
@@ -407,7 +469,7 @@ class Prefetch {
                         rd_ok = ahead_ok_;
                     } else {
                         if (ahead_want_) reader_.wait();
-                        raw.resize(want);
+                        if (!raw.resize(want, inf_)) return delete c, set_fail("out of host memory");
                         rd_ok = pread_all(bam_->fd, raw.data(), want, coff_);
                     }
                     ahead_want_ = 0;
@@ -429,6 +491,7 @@ class Prefetch {
                         b.isize = rd32(raw.data() + p + bs - 4);
                         if (b.isize > 65536 || bs < 12u + rd16(raw.data() + p + 10) + 8u)
                             return delete c, set_fail("corrupt BGZF block at offset " + std::to_string(coff_ + p));
+                        if (inf_.run && !blocks.empty() && total + b.isize > kMaxInflated) break;  // next chunk
                         b.out_off = total;
                         total += b.isize;
                         blocks.push_back(b);
@@ -441,32 +504,76 @@ class Prefetch {
                             ahead_coff_ = coff_ + p;
                             ahead_want_ = (size_t)std::min<uint64_t>(want_c, (uint64_t)bam_->file_size - ahead_coff_);
                             reader_.submit([this] {
-                                ahead_.resize(ahead_want_);
-                                ahead_ok_ = pread_all(bam_->fd, ahead_.data(), ahead_want_, ahead_coff_);
+                                ahead_ok_ = ahead_.resize(ahead_want_, inf_) &&
+                                            pread_all(bam_->fd, ahead_.data(), ahead_want_, ahead_coff_);
                             });
                         }
                         if (kHead + total > c->cap) {
                             c->cap = kHead + total + (total >> 3);
-                            c->mem.reset(new (std::nothrow) uint8_t[c->cap]);
-                            if (!c->mem) return delete c, set_fail("out of host memory");
+                            if (!c->mem.alloc(c->cap, inf_)) {
+                                c->cap = 0;
+                                return delete c, set_fail("out of host memory");
+                            }
                         }
                         std::atomic<size_t> next{0};
                         std::atomic<bool> ok{true};
                         const int nt = std::max(1, std::min<int>(pool_.size(), (int)blocks.size()));
                         uint8_t* out = c->mem.get() + kHead;
                         const double ti0 = now_s();
-                        pool_.run(nt, [&](int) {
-                            mgp_host::Inflator inf;
-                            for (;;) {
-                                const size_t i = next.fetch_add(1);
-                                if (i >= blocks.size()) break;
+                        const uint8_t* rawp = raw.data();
+                        if (inf_.run) {
+                            // the whole chunk in one call of the inflater (the raw deflate range of
+                            // each block: past its 12 + XLEN header, before its 8-byte trailer), then
+                            // the pool checks every status and CRC
+                            const size_t nb = blocks.size();
+                            h_coff_.resize(nb);
+                            h_ooff_.resize(nb);
+                            h_clen_.resize(nb);
+                            h_isize_.resize(nb);
+                            h_status_.assign(nb, -1);
+                            for (size_t i = 0; i < nb; ++i) {
                                 const Block& b = blocks[i];
-                                if (!inflate_block(raw.data() + b.coff, b.csize, out + b.out_off, b.isize, inf)) {
-                                    ok = false;
-                                    break;
-                                }
+                                const uint32_t hdr = 12u + rd16(rawp + b.coff + 10);
+                                h_coff_[i] = b.coff + hdr;
+                                h_clen_[i] = b.csize - hdr - 8;
+                                h_isize_[i] = b.isize;
+                                h_ooff_[i] = b.out_off;
                             }
-                        });
+                            const int rc = inf_.run(inf_.ctx, rawp, (int64_t)p, (int64_t)nb, h_coff_.data(), h_clen_.data(),
+                                                    h_isize_.data(), h_ooff_.data(), out, (int64_t)total,
+                                                    h_status_.data());
+                            if (rc != 0) {
+                                const char* m = inf_.message ? inf_.message() : nullptr;
+                                t_inflate += now_s() - ti0;
+                                return delete c, set_fail("BGZF inflater failed (" + std::to_string(rc) + ") in " +
+                                                          bam_->path + (m && *m ? std::string(": ") + m : std::string()));
+                            }
+                            pool_.run(nt, [&](int) {
+                                for (;;) {
+                                    const size_t i = next.fetch_add(1);
+                                    if (i >= nb) break;
+                                    const Block& b = blocks[i];
+                                    if (h_status_[i] != 0 || mgp_host::crc32_any(0, out + b.out_off, b.isize) !=
+                                                                 rd32(rawp + b.coff + b.csize - 8)) {
+                                        ok = false;
+                                        break;
+                                    }
+                                }
+                            });
+                        } else {
+                            pool_.run(nt, [&](int) {
+                                mgp_host::Inflator inf;
+                                for (;;) {
+                                    const size_t i = next.fetch_add(1);
+                                    if (i >= blocks.size()) break;
+                                    const Block& b = blocks[i];
+                                    if (!inflate_block(rawp + b.coff, b.csize, out + b.out_off, b.isize, inf)) {
+                                        ok = false;
+                                        break;
+                                    }
+                                }
+                            });
+                        }
                         t_inflate += now_s() - ti0;
                         if (!ok) return delete c, set_fail("BGZF inflate/CRC error in " + bam_->path);
                         c->n = total;
@@ -520,10 +627,14 @@ class Prefetch {
     }
     mgp_bam* bam_;
     uint64_t coff_;
+    const mgp_bam_inflater inf_;  // the bam's inflater when this prefetch began (run == NULL: the host's)
+    std::vector<uint64_t> h_coff_, h_ooff_;  // the inflater's block tables of a chunk
+    std::vector<uint32_t> h_clen_, h_isize_;
+    std::vector<int32_t> h_status_;
     mgp_host::Pool pool_;  // (before th_: alive while run() uses it)
     Worker walker_;        // (likewise)
     Worker reader_;        // (likewise; its read targets ahead_)
-    std::vector<uint8_t> ahead_;
+    RawBytes ahead_;
     uint64_t ahead_coff_ = 0;
     size_t ahead_want_ = 0;  // 0: no read ahead pending
     bool ahead_ok_ = false;
@@ -1638,6 +1749,18 @@ int mgp_bam_set_barcodes(mgp_bam* b, const char* tag, const char* const* barcode
     }
     b->wl.build(k, v);
     b->bulk_cell = -1;
+    return 0;
+}
+
+int mgp_bam_set_inflater(mgp_bam* b, const mgp_bam_inflater* inf) {
+    if (!b) return fail("null argument");
+    if (!inf) {
+        b->inflater = mgp_bam_inflater{nullptr, nullptr, nullptr, nullptr, nullptr};
+        return 0;
+    }
+    if (!inf->run) return fail("an inflater needs its run function");
+    if (!inf->alloc != !inf->release) return fail("an inflater gives both alloc and release, or neither");
+    b->inflater = *inf;
     return 0;
 }
 

@@ -45,7 +45,8 @@ ABI_SYMBOLS = (
     "mgp_cell_coverage_run", "mgp_position_coverage_run", "mgp_position_depth_hist_run",
     "mgp_position_depth_next_run", "mgp_cell_coverage_rows", "mgp_position_coverage_rows",
     "mgp_position_depth_hist_rows", "mgp_position_depth_next_rows", "mgp_pair_dist", "mgp_hclust_dist", "mgp_hclust",
-    "mgp_knn", "mgp_snn",
+    "mgp_knn", "mgp_snn", "mgp_bgzf_inflate", "mgp_inflater_create", "mgp_inflater_destroy", "mgp_inflater_run",
+    "mgp_inflater_host_alloc", "mgp_inflater_host_release", "mgp_inflater_times",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -319,6 +320,13 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_hclust": ([C.c_int, vp, i64, i64, vp, vp, vp, vp], C.c_int),
         "mgp_knn": ([C.c_int, vp, i64, i64, i32, vp, vp], C.c_int),
         "mgp_snn": ([C.c_int, vp, i64, i32, i32, i64, C.POINTER(i64), vp, vp, vp], C.c_int),
+        "mgp_bgzf_inflate": ([C.c_int, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp], C.c_int),
+        "mgp_inflater_create": ([C.c_int, i64, i64, C.POINTER(vp)], C.c_int),
+        "mgp_inflater_destroy": ([vp], None),
+        "mgp_inflater_run": ([vp, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp], C.c_int),
+        "mgp_inflater_host_alloc": ([i64], vp),
+        "mgp_inflater_host_release": ([vp], None),
+        "mgp_inflater_times": ([vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -862,6 +870,90 @@ def graph_snn(idx, min_shared: int, device: int = 0):
         order = np.lexsort((out[1], out[0]))
         out = [a[order] for a in out]
     return tuple(out)
+
+
+INFLATE_MAX_ISIZE = 65536  # inflated bytes of one BGZF block
+
+
+def _inflate_args(src, coff, clen, isize, out_off, out):
+    """The arrays of one inflate call in the C-ABI's types, and the statuses' array."""
+    src = np.ascontiguousarray(np.frombuffer(src, np.uint8) if isinstance(src, (bytes, bytearray)) else src, np.uint8)
+    coff = np.ascontiguousarray(coff, np.uint64)
+    clen = np.ascontiguousarray(clen, np.uint32)
+    isize = np.ascontiguousarray(isize, np.uint32)
+    out_off = np.ascontiguousarray(out_off, np.uint64)
+    n = int(coff.shape[0])
+    if not (clen.shape[0] == isize.shape[0] == out_off.shape[0] == n):
+        raise InvalidInputError("coff, clen, isize and out_off have one entry per block")
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise InvalidInputError("out is a writable contiguous uint8 array")
+    status = np.full(n, -1, np.int32)
+    return (_ptr(src), int(src.shape[0]), n, _ptr(coff), _ptr(clen), _ptr(isize), _ptr(out_off), _ptr(out),
+            int(out.shape[0]), _ptr(status)), status, (src, coff, clen, isize, out_off)
+
+
+def inflate_bgzf(src, coff, clen, isize, out_off, out: np.ndarray, device: int = 0) -> np.ndarray:
+    """mgp_bgzf_inflate: block i is the raw deflate stream src[coff[i], coff[i] + clen[i]) and
+    inflates to isize[i] bytes at out[out_off[i], ...) on the device; returns the blocks'
+    statuses (0 ok, 1 invalid stream, 2 wrong size or input ended early). CRC32 is the
+    caller's."""
+    args, status, keep = _inflate_args(src, coff, clen, isize, out_off, out)
+    _ck(load_library().mgp_bgzf_inflate(int(device), *args), "mgp_bgzf_inflate")
+    del keep
+    return status
+
+
+class Inflater:
+    """An mgp_inflater: device buffers for max_src_bytes / max_out_bytes per call, a stream
+    and pinned staging kept across calls (the BAM ingest's form, BamFile.set_device_inflate)."""
+
+    def __init__(self, device: int = 0, max_src_bytes: int = 20 << 20, max_out_bytes: int = 80 << 20):
+        self.lib = load_library()
+        self.device = int(device)
+        self.max_src_bytes, self.max_out_bytes = int(max_src_bytes), int(max_out_bytes)
+        h = C.c_void_p()
+        _ck(self.lib.mgp_inflater_create(self.device, self.max_src_bytes, self.max_out_bytes, C.byref(h)),
+            "mgp_inflater_create")
+        self._h = h
+
+    @property
+    def handle(self) -> int:
+        """The mgp_inflater's address (the ctx of mgp_inflater_run)."""
+        if not self._h:
+            raise ProcessingError("the inflater is closed")
+        return int(self._h.value)
+
+    def run(self, src, coff, clen, isize, out_off, out: np.ndarray) -> np.ndarray:
+        """mgp_inflater_run: as :func:`inflate_bgzf`."""
+        args, status, keep = _inflate_args(src, coff, clen, isize, out_off, out)
+        _ck(self.lib.mgp_inflater_run(self.handle, *args), "mgp_inflater_run")
+        del keep
+        return status
+
+    def times(self) -> dict:
+        """mgp_inflater_times: the calls' device milliseconds so far (H2D, kernel, D2H), summed."""
+        ms = (C.c_double * 3)()
+        calls, blocks = C.c_int64(0), C.c_int64(0)
+        _ck(self.lib.mgp_inflater_times(self.handle, ms, C.byref(calls), C.byref(blocks)), "mgp_inflater_times")
+        return {"h2d_ms": ms[0], "kernel_ms": ms[1], "d2h_ms": ms[2], "calls": int(calls.value),
+                "blocks": int(blocks.value)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.mgp_inflater_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Engine:

@@ -369,6 +369,7 @@ def run_pipeline(
     clones: int | None = None,
     neighbors: int | None = None,
     snn_prune: float = 1.0 / 15.0,
+    device_inflate: bool = False,
 ) -> dict[str, Any]:
     """pipeline.py:183-269. ``min_distance_from_end`` is accepted and, as in the
     reference, not passed on (the engine uses 5). ``call_variants``
@@ -384,7 +385,8 @@ def run_pipeline(
     cell tree cut into K clones. ``neighbors`` = K (needs ``call_variants``; Seurat's k.param, 2..65)
     builds the cells' kNN graph over the variants and its SNN graph (Jaccard weights, ``snn_prune``
     as Seurat's prune.SNN) on the device and writes variants/cell_knn.tsv, cell_snn.mtx and
-    cell_snn_barcodes.tsv."""
+    cell_snn_barcodes.tsv. ``device_inflate`` inflates the BAM's BGZF blocks on the device (the
+    first of ``devices``) instead of the host pool; the outputs are the same bytes."""
     barcode_metadata = None
     if barcode_file is None:
         from .file_io.barcode_extraction import extract_barcodes_from_bam
@@ -414,6 +416,7 @@ def run_pipeline(
         n_cores=n_cores, worker_batch_size=worker_batch_size, io_batch_size=io_batch_size,
         max_memory_gb=max_memory_gb, sequential=sequential, min_reads_per_cell=min_reads_per_cell,
         barcode_tag=barcode_tag, mito_chr=mito_chr, write_cell_bams=write_cell_bams,
+        device_inflate=device_inflate, inflate_device=devices[0] if devices else device,
     )
     pipeline = MtDNAPipeline(
         bam_path=bam_path, barcodes=barcodes, output_dir=Path(output_dir), config=config,

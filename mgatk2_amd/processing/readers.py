@@ -50,7 +50,14 @@ class BAMReader:
         self._validate_bam_file()
 
     def _open(self) -> BamFile:
-        return BamFile(self.bam_path, n_threads=self.n_threads)
+        bam = BamFile(self.bam_path, n_threads=self.n_threads)
+        if getattr(self.config, "device_inflate", False):
+            try:
+                bam.set_device_inflate(self.config.inflate_device)
+            except Exception:
+                bam.close()
+                raise
+        return bam
 
     def _validate_bam_file(self):
         """readers.py:35-61: mito contig (first of MITO_NAMES present wins over
