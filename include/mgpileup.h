@@ -70,6 +70,8 @@ extern "C" {
                                  heteroplasmy on the device),
                                  mgp_knn, mgp_snn (the cells' kNN and SNN graphs by heteroplasmy
                                  on the device),
+                                 mgp_louvain (Louvain communities of such a graph on the device:
+                                 the cells' clonotypes),
                                  mgp_bgzf_inflate, mgp_inflater_* (BGZF inflate on the device) */
 
 /* ---- return codes (0 = success) ------------------------------------------ */
@@ -753,7 +755,7 @@ int  mgp_hclust(int device, const double *x, int64_t n_items, int64_t n_feat, in
 /* The cells' neighbour graphs by heteroplasmy on the device (added under ABI 7): the step of
  * the vignette's "Integration with Seurat/Signac", Signac's FindClonotypes -> FindNeighbors, a
  * k-nearest-neighbour graph of the cells over the variants and Seurat's ComputeSNN on it (the
- * input of FindClusters, igraph or leidenalg; community detection itself is not done here). No
+ * input of FindClusters, igraph or leidenalg, and of mgp_louvain below). No
  * engine context, buffers of the call's own, all freed on return (MGP_E_OOM leaves nothing
  * allocated). Items are the columns of x [n_feat][n_items] as for mgp_pair_dist, every value
  * finite (MGP_E_INVALID otherwise), and the distance of a pair is the number mgp_pair_dist
@@ -785,6 +787,61 @@ int  mgp_knn(int device, const double *x, int64_t n_items, int64_t n_feat, int32
 int  mgp_snn(int device, const int32_t *knn_idx /* [n][k] */, int64_t n_items, int32_t k, int32_t min_shared,
              int64_t capacity, int64_t *n_edges, int32_t *out_i, int32_t *out_j,
              int32_t *out_shared /* [capacity] each, may be NULL when capacity == 0 */);
+/* Louvain communities of an integer-weighted graph on the device (added under ABI 7): the second
+ * half of Signac's FindClonotypes, FindClusters on the SNN graph, which gives each cell its
+ * clonotype. The CPU tools visit the vertices one by one in a random order; here a pass is
+ * synchronous and every sum an integer sum, so the result is a function of the input alone
+ * (DESIGN.md 7.10). No engine context, buffers of the call's own, all freed on return.
+ * Input. n_vertices vertices and n_edges undirected edges (edge_i[e], edge_j[e]), i < j, each
+ * pair once, with a weight edge_w[e] in 1..2^20 in units of 2^-20 (the caller quantises once:
+ * floor(weight * 2^20 + 0.5); for mgp_snn's graph the Jaccard weight). No self-loops; the SNN's
+ * implicit diagonal is left out, as Seurat's RunModularityClusteringCpp leaves it out.
+ * Exact sums. d_v = the sum of v's edge weights, M2 = the sum of all d_v <= 2^51. Degrees,
+ * community totals, vertex-to-community weights, coarse edge weights and internal weights are
+ * integer sums: exact and independent of the order in which the device's atomics add them.
+ * Level. Vertices with degree d_v, self weight self_v (twice the internal weight collapsed into
+ * v; 0 at level 0), an integer-weighted adjacency, labels c_v = v and tot_c = the sum of d_v over
+ * the members of c. The level's best score starts as the score (below) of these labels.
+ * Pass p = 0, 1, ... of a level. Every vertex decides from the same snapshot of the labels and
+ * tot. With a its community, k_vb the sum of its edge weights into community b (self weight
+ * excluded) and g1 = resolution * double(d_v):
+ *   stay  = double(k_va) * double(M2) - g1 * double(tot_a - d_v)
+ *   go(b) = double(k_vb) * double(M2) - g1 * double(tot_b)   for every other neighbouring b with
+ *           b < a on even p and b > a on odd p (the direction rule keeps two vertices from
+ *           swapping for ever; it replaces any special case for singletons),
+ * every product and difference one IEEE fp64 operation rounded on its own (no fma). The vertex
+ * moves to the b of largest go, the smallest such b on a tie, if go(b) > stay. All moves are
+ * applied together and tot is recomputed.
+ * Score. I = the sum over communities of in_c, in_c = the sum over v in c of self_v + v's edge
+ * weights to members of c; B = the sum of tot_c^2, an exact integer below 2^102 (the device
+ * returns exact (hi, lo) partial sums, the host adds them in 128 bits);
+ *   S = double(M2) * double(I) - resolution * double(B),   Q = S / double(M2) / double(M2)
+ * with double(B) the correctly rounded conversion and each operation rounded on its own.
+ * A pass is accepted if it moved a vertex and S is above the level's best S; otherwise it is
+ * undone (labels and tot as before). A level ends after two undone passes in a row or after
+ * max_passes passes.
+ * Aggregation. The non-empty communities in ascending label order are the next level's vertices
+ * 0..n'-1 with d = tot_c, self = in_c and the integer sums between communities as edge weights.
+ * The call ends when a level merges nothing (n' = its vertices), when n' = 1, or after max_levels
+ * levels. Vertices without edges stay alone; n_edges == 0 launches nothing (every vertex its own
+ * community, Q = 0, no level).
+ * Output. labels [n_vertices]: communities numbered from 0 by descending size, ties by smallest
+ * member; *n_communities; *modularity = Q; sums [4] = M2, I, B's high and low 64 bits;
+ * *n_levels and levels [max_levels][4] = (vertices, communities, passes, accepted passes) of
+ * each level run.
+ * Refused (MGP_E_INVALID) before any allocation or launch: null pointers, negative counts,
+ * n_vertices > 2^20, n_edges > 2^30, a resolution that is not finite or not above 0, max_levels
+ * outside 1..64, max_passes outside 1..65,536; and by the device's checks before the first level:
+ * an edge that is not i < j with both in range, a repeated pair, a weight outside 1..2^20.
+ * The move kernel takes a row (a vertex's entries) as a wave when it has at most
+ * MGP_LOUVAIN_WAVE_ROW entries (64), as a workgroup with a table in LDS up to MGP_LOUVAIN_LDS_ROW
+ * (2,048) and with a table in global memory above; both are read from the environment at call
+ * time (0..64 and 0..2,048; anything else: the default) and change no result.
+ * Device memory, m = 2 n_edges: 12 n_edges + 56 m + about 120 n_vertices bytes. */
+int  mgp_louvain(int device, int64_t n_vertices, int64_t n_edges, const int32_t *edge_i, const int32_t *edge_j,
+                 const int32_t *edge_w, double resolution, int32_t max_levels, int32_t max_passes,
+                 int32_t *labels /* [n_vertices] */, int64_t *n_communities, double *modularity,
+                 uint64_t *sums /* [4] */, int32_t *n_levels, int64_t *levels /* [max_levels][4] */);
 /* Position windows of the pileup (the `wide` flags' second dimension). */
 int  mgp_windows(mgp_ctx *ctx, int32_t *n_windows, int32_t *window_width);
 /* Wait until the H2D copies of every batch pushed so far have completed: the caller may

@@ -4,8 +4,8 @@ The step of mgatk's vignette after the heatmap, "Integration with Seurat/Signac"
 ``FindClonotypes`` calls ``FindNeighbors`` on the heteroplasmy matrix, a kNN graph of the cells
 over the variants and Seurat's ``ComputeSNN`` on it, and gives the SNN graph to a graph clusterer.
 The device makes both graphs (``mgp_knn`` / ``mgp_snn``, mgp_graph.hip) without the n x n
-distance matrix; community detection is randomised in those tools and is left to them
-(``FindClusters``, igraph, leidenalg all take the graph written here).
+distance matrix. Community detection on the SNN graph is :mod:`.clonotypes` (a deterministic
+Louvain on the device); ``FindClusters``, igraph and leidenalg also take the graph written here.
 
 Definitions (include/mgpileup.h). Items are the columns of ``x [n_feat, n_items]``. The distance
 of a pair is the number ``pair_dist`` gives for it, bit for bit. Row i of the kNN holds the k

@@ -8,7 +8,9 @@ and ``--coverage-stats`` / ``--cell-min-mean-coverage`` / ``--cell-min-coverage-
 ``--recompute-reference`` (coverage QC and the cell filter from the device's rows, coverage/),
 and ``--cluster`` / ``--clones K`` (the heteroplasmy matrix's cells and variants clustered on
 the device, the trees and heatmap orders in variants/), and ``--neighbors K`` / ``--snn-prune P``
-(the cells' kNN and SNN graphs by heteroplasmy on the device, in variants/).
+(the cells' kNN and SNN graphs by heteroplasmy on the device, in variants/), and ``--clonotypes`` /
+``--clonotype-resolution R`` (the Louvain communities of that SNN graph on the device: each cell's
+clonotype, in variants/).
 Not carried over: ``hardmask-fasta`` (FASTA masking utility, outside the hot path).
 """
 
@@ -72,6 +74,12 @@ def _variant_options(f):
         click.option("--snn-prune", default=None, type=click.FloatRange(min=0.0, max=1.0), metavar="P",
                      help="Drop SNN edges of Jaccard weight below P (Seurat's prune.SNN)  [default: 1/15]; "
                           "needs --neighbors"),
+        click.option("--clonotypes", is_flag=True,
+                     help="Clonotypes of the cells: Louvain communities of the SNN graph on the device, the same "
+                          "on every run (variants/cell_clonotypes.tsv, clonotypes.tsv); needs --neighbors"),
+        click.option("--clonotype-resolution", default=None, type=float, metavar="R",
+                     help="Resolution of the communities, as Seurat's: above 1 more and smaller clonotypes  "
+                          "[default: 1.0]; needs --clonotypes"),
         click.option("--device-inflate", "device_inflate", is_flag=True,
                      help="Inflate the BAM's BGZF blocks on the device (the first of --devices); CRC32 stays on "
                           "the host. Off by default"),
@@ -84,17 +92,25 @@ def _variant_options(f):
 def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
                   variant_low_coverage, variant_min_coverage, coverage_stats=False, cell_min_mean_coverage=0.0,
                   cell_min_coverage_breadth=0.0, recompute_reference=False, cluster=False, clones=None, neighbors=None,
-                  snn_prune=None, device_inflate=False) -> dict:
+                  snn_prune=None, clonotypes=False, clonotype_resolution=None, device_inflate=False) -> dict:
     """The options run_pipeline gets beyond the reference's, each only when asked for: the
     variant options with --variants; the four coverage options with --coverage-stats,
     otherwise the filter thresholds and --recompute-reference that were given; --cluster and
     --clones when given (--cluster needs --variants, --clones needs --cluster: a usage error);
     --neighbors and --snn-prune when given (--neighbors needs --variants, --snn-prune needs
-    --neighbors: a usage error); --device-inflate when given."""
+    --neighbors: a usage error); --clonotypes and --clonotype-resolution when given (--clonotypes
+    needs --neighbors, --clonotype-resolution needs --clonotypes and a finite value above 0: a
+    usage error); --device-inflate when given."""
     if neighbors is not None and not call_variants:
         raise click.UsageError("--neighbors requires --variants")
     if snn_prune is not None and neighbors is None:
         raise click.UsageError("--snn-prune requires --neighbors")
+    if clonotypes and neighbors is None:
+        raise click.UsageError("--clonotypes requires --neighbors")
+    if clonotype_resolution is not None and not clonotypes:
+        raise click.UsageError("--clonotype-resolution requires --clonotypes")
+    if clonotype_resolution is not None and not (0.0 < float(clonotype_resolution) < float("inf")):
+        raise click.UsageError("--clonotype-resolution must be finite and above 0")
     if cluster and not call_variants:
         raise click.UsageError("--cluster requires --variants")
     if clones is not None and not cluster:
@@ -122,6 +138,10 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
         out.update(neighbors=int(neighbors))
         if snn_prune is not None:
             out.update(snn_prune=float(snn_prune))
+    if clonotypes:
+        out.update(clonotypes=True)
+        if clonotype_resolution is not None:
+            out.update(clonotype_resolution=float(clonotype_resolution))
     if device_inflate:
         out.update(device_inflate=True)
     return out
@@ -337,6 +357,9 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
         if variant_args and variant_args.get("neighbors") is not None:
             logger.info("  Neighbour graph:        k.param %s, SNN prune %s", variant_args["neighbors"],
                         variant_args.get("snn_prune", "1/15"))
+        if variant_args and variant_args.get("clonotypes"):
+            logger.info("  Clonotypes:             Louvain on the SNN graph, resolution %s",
+                        variant_args.get("clonotype_resolution", 1.0))
         if variant_args and variant_args.get("device_inflate"):
             logger.info("  BGZF inflate:           on the device")
         if dry_run:

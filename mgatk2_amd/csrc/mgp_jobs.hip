@@ -5,7 +5,8 @@
 // through run_rows (mgp_jobs.h: the context itself is opaque here), and the detached
 // *_rows form on u32 rows of the caller's (on_rows). The clustering of the heteroplasmy
 // matrix (mgp_cluster.hip) reads no rows and needs no context: mgp_pair_dist / mgp_hclust*;
-// nor do the cells' neighbour graphs (mgp_graph.hip): mgp_knn / mgp_snn.
+// nor do the cells' neighbour graphs (mgp_graph.hip): mgp_knn / mgp_snn; nor the communities of
+// such a graph (mgp_louvain.hip): mgp_louvain.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +20,7 @@
 #include "mgp_graph.h"
 #include "mgp_host.h"
 #include "mgp_jobs.h"
+#include "mgp_louvain.h"
 #include "mgp_qc.h"
 #include "mgp_txtgz.h"
 #include "mgp_variants.h"
@@ -60,6 +62,14 @@ struct ClusterState {
 struct GraphState {
     DevBuf x, bad, part_dist, part_idx, out_dist, out_idx;                 // mgp_knn
     DevBuf idx, sets, deg, off, cur, rev, cnt, eoff, ei, ej, es;  // mgp_snn
+};
+
+// mgp_louvain: the community detection's buffers (mgp_louvain.hip), a call's own
+struct LouvainState {
+    DevBuf ei, ej, wq, res, deg, cur, tkeys, tvals;                // the edge list, the results' words, the tables
+    DevBuf off[2], nbr[2], src[2], w[2], d[2], self[2];            // this level's graph and the next one's
+    DevBuf c, next, tot, tot_next, list_mid, list_long, counts;    // a level's labels, totals and row lists
+    DevBuf flag, ren, cap, slot, map;                              // the aggregation
 };
 
 struct RowJobs {
@@ -1137,6 +1147,234 @@ int mgp_snn(int device, const int32_t* knn_idx, int64_t n_items, int32_t k, int3
         HIP_TRY(hipMemcpyAsync(out_shared, st.es.p, ne * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         fill.report(who, "items, edges, fill pass", n_items, total);
+        return (int)MGP_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// mgp_louvain: the communities of an integer-weighted graph, the cells' clonotypes when the graph
+// is mgp_snn's (Signac's FindClonotypes -> FindClusters). The definition is pinned in
+// include/mgpileup.h; the loop of levels and passes runs here, and per pass only the moved
+// count, the bad word, I and the partial sums of tot^2 come back. No engine context, as the graphs.
+// ---------------------------------------------------------------------------
+// S = double(M2) * double(I) - gamma * double(B): two products and a difference, each rounded on
+// its own; the conversion of the 128-bit B is the compiler's correctly rounded one
+static double lv_score(uint64_t m2, uint64_t internal, unsigned __int128 b, double gamma) {
+#pragma clang fp contract(off)
+    const double x = (double)m2 * (double)internal;
+    const double y = gamma * (double)b;
+    return x - y;
+}
+
+// an integer threshold from the environment, read at call time: unset or not in lo..hi gives dflt
+static int lv_env(const char* name, int lo, int hi, int dflt) {
+    const char* e = std::getenv(name);
+    if (!e || !*e) return dflt;
+    const long v = std::strtol(e, nullptr, 10);
+    return v < lo || v > hi ? dflt : (int)v;
+}
+
+int mgp_louvain(int device, int64_t n_vertices, int64_t n_edges, const int32_t* edge_i, const int32_t* edge_j,
+                const int32_t* edge_w, double resolution, int32_t max_levels, int32_t max_passes, int32_t* labels,
+                int64_t* n_communities, double* modularity, uint64_t* sums, int32_t* n_levels, int64_t* levels) {
+    const char* who = "mgp_louvain";
+    if (n_communities) *n_communities = 0;
+    if (n_levels) *n_levels = 0;
+    if (n_vertices < 0 || n_edges < 0 || !n_communities || !modularity || !sums || !n_levels || !levels ||
+        (n_vertices > 0 && !labels) || (n_edges > 0 && (!edge_i || !edge_j || !edge_w)))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    if (n_vertices > louvain::kMaxVertices)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^20 vertices in one call");
+    if (n_edges > louvain::kMaxEdges)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^30 edges in one call");
+    if (!(resolution > 0.0) || !(resolution <= 1.7976931348623157e308))
+        return set_err(MGP_E_INVALID, std::string(who) + ": the resolution must be finite and above 0");
+    if (max_levels < 1 || max_levels > louvain::kMaxLevels)
+        return set_err(MGP_E_INVALID, std::string(who) + ": max_levels must be in 1..64");
+    if (max_passes < 1 || max_passes > louvain::kMaxPasses)
+        return set_err(MGP_E_INVALID, std::string(who) + ": max_passes must be in 1..65536");
+    if (n_edges > 0 && n_vertices < 2)
+        return set_err(MGP_E_INVALID, std::string(who) + ": an edge needs two vertices");
+    *modularity = 0.0;
+    sums[0] = sums[1] = sums[2] = sums[3] = 0;
+    if (n_edges == 0) {  // nothing is launched: every vertex its own community
+        for (int64_t v = 0; v < n_vertices; ++v) labels[v] = (int32_t)v;
+        *n_communities = n_vertices;
+        return MGP_OK;
+    }
+    // the move kernel's thresholds (rows up to the first: a wave; up to the second: the LDS table)
+    const int wave_row = lv_env("MGP_LOUVAIN_WAVE_ROW", 0, louvain::kWaveRow, louvain::kWaveRow);
+    const int lds_row = lv_env("MGP_LOUVAIN_LDS_ROW", 0, louvain::kLdsRow, louvain::kLdsRow);
+    return cl_call<LouvainState>(device, [&](LouvainState& st, hipStream_t s) {
+        using namespace louvain;
+        const int n0 = (int)n_vertices;
+        const size_t un = (size_t)n_vertices, ne = (size_t)n_edges, m0 = 2 * ne;
+        const size_t res_bytes = 16 + (size_t)kScoreBlocks * 16;  // moved, bad, I, the (hi, lo) pairs
+        for (DevBuf* b : {&st.ei, &st.ej, &st.wq}) MGP_TRY(b->ensure(ne * 4));
+        MGP_TRY(st.res.ensure(res_bytes));
+        for (DevBuf* b : {&st.deg, &st.cur, &st.c, &st.next, &st.list_mid, &st.list_long, &st.flag, &st.map})
+            MGP_TRY(b->ensure(un * 4));
+        for (DevBuf* b : {&st.tot, &st.tot_next, &st.cap, &st.d[0], &st.d[1], &st.self[0], &st.self[1]})
+            MGP_TRY(b->ensure(un * 8));
+        for (DevBuf* b : {&st.ren, &st.slot, &st.off[0], &st.off[1]}) MGP_TRY(b->ensure((un + 1) * 8));
+        MGP_TRY(st.counts.ensure(8));
+        for (int k = 0; k < 2; ++k) {
+            MGP_TRY(st.nbr[k].ensure(m0 * 4));
+            MGP_TRY(st.src[k].ensure(m0 * 4));
+            MGP_TRY(st.w[k].ensure(m0 * 8));
+        }
+        MGP_TRY(st.tkeys.ensure(2 * m0 * 4));
+        MGP_TRY(st.tvals.ensure(2 * m0 * 8));
+        int32_t* moved = st.res.as<int32_t>();
+        uint32_t* bad = st.res.as<uint32_t>() + 1;
+        uint64_t* internal = st.res.as<uint64_t>() + 1;
+        uint64_t* partial = st.res.as<uint64_t>() + 2;
+        Csr g[2];
+        for (int k = 0; k < 2; ++k)
+            g[k] = Csr{st.off[k].as<int64_t>(), st.nbr[k].as<int32_t>(), st.src[k].as<int32_t>(), st.w[k].as<uint64_t>()};
+        HIP_TRY(hipMemcpyAsync(st.ei.p, edge_i, ne * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(st.ej.p, edge_j, ne * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(st.wq.p, edge_w, ne * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(st.res.p, 0, res_bytes, s));
+        std::vector<int32_t> iota(un);
+        for (size_t v = 0; v < un; ++v) iota[v] = (int32_t)v;
+        HIP_TRY(hipMemcpyAsync(st.map.p, iota.data(), un * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(st.self[0].p, 0, un * 8, s));
+
+        // ---- build: the checks, the degrees, the symmetric CSR, the repeated pairs
+        VarProf build(s);
+        if (build_degrees(st.ei.as<int32_t>(), st.ej.as<int32_t>(), st.wq.as<int32_t>(), n_edges, n0,
+                          st.deg.as<int32_t>(), st.d[0].as<uint64_t>(), bad, s) != 0 ||
+            scan32(st.deg.as<int32_t>(), n0, g[0].off, s) != 0 ||
+            build_fill(st.ei.as<int32_t>(), st.ej.as<int32_t>(), st.wq.as<int32_t>(), n_edges, n0, st.cur.as<int32_t>(),
+                       g[0], s) != 0 ||
+            build_repeats(g[0], (int64_t)m0, st.tkeys.as<int32_t>(), bad, s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": build kernel launch failed");
+        build.stop();
+        std::vector<uint64_t> res(res_bytes / 8);
+        const auto fetch = [&]() -> int {
+            HIP_TRY(hipMemcpyAsync(res.data(), st.res.p, res_bytes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            return MGP_OK;
+        };
+        const auto res_bad = [&]() { return (uint32_t)(res[0] >> 32); };
+        const auto res_moved = [&]() { return (int64_t)(res[0] & 0xFFFFFFFFu); };
+        const auto res_b = [&]() {
+            unsigned __int128 b = 0;
+            for (int k = 0; k < kScoreBlocks; ++k) b += ((unsigned __int128)res[2 + 2 * k] << 64) | res[3 + 2 * k];
+            return b;
+        };
+        MGP_TRY(fetch());
+        build.report(who, "vertices, edges, build", n_vertices, n_edges);
+        if (res_bad() & BAD_EDGE)
+            return set_err(MGP_E_INVALID, std::string(who) + ": an edge is not i < j with both in [0, n_vertices)");
+        if (res_bad() & BAD_WEIGHT)
+            return set_err(MGP_E_INVALID, std::string(who) + ": a weight is outside 1..2^20");
+        if (res_bad() & BAD_REPEAT) return set_err(MGP_E_INVALID, std::string(who) + ": a pair is repeated");
+        if (res_bad()) return set_err(MGP_E_HIP, std::string(who) + ": a table overflowed in the build");
+        uint64_t m2 = 0;
+        for (size_t e = 0; e < ne; ++e) m2 += 2 * (uint64_t)edge_w[e];
+
+        // ---- the levels
+        VarProf run(s);
+        int cur = 0, nl = n0, n_lv = 0;
+        int64_t m = (int64_t)m0, total_passes = 0;
+        uint64_t best_i = 0;
+        unsigned __int128 best_b = 0;
+        int32_t *c = st.c.as<int32_t>(), *next = st.next.as<int32_t>();
+        uint64_t *tot = st.tot.as<uint64_t>(), *tot_next = st.tot_next.as<uint64_t>();
+        while (true) {
+            const uint64_t* d = st.d[cur].as<uint64_t>();
+            const uint64_t* self = st.self[cur].as<uint64_t>();
+            int32_t counts[2] = {0, 0};
+            if (level_start(g[cur], nl, d, c, tot, wave_row, lds_row, st.list_mid.as<int32_t>(),
+                            st.list_long.as<int32_t>(), st.counts.as<int32_t>(), s) != 0 ||
+                score(g[cur], m, nl, c, self, tot, internal, partial, s) != 0)
+                return set_err(MGP_E_HIP, std::string(who) + ": level kernel launch failed");
+            HIP_TRY(hipMemcpyAsync(counts, st.counts.p, 8, hipMemcpyDeviceToHost, s));
+            MGP_TRY(fetch());
+            best_i = res[1];
+            best_b = res_b();
+            double best = lv_score(m2, best_i, best_b, resolution);
+            int passes = 0, accepted = 0, undone = 0;
+            while (passes < max_passes && undone < 2) {
+                HIP_TRY(hipMemcpyAsync(next, c, (size_t)nl * 4, hipMemcpyDeviceToDevice, s));
+                if (move(g[cur], nl, c, tot, d, m2, resolution, passes & 1, wave_row, st.list_mid.as<int32_t>(),
+                         counts[0], st.list_long.as<int32_t>(), counts[1], st.tkeys.as<int32_t>(),
+                         st.tvals.as<uint64_t>(), next, bad, s) != 0 ||
+                    apply(nl, c, next, d, tot_next, moved, s) != 0 ||
+                    score(g[cur], m, nl, next, self, tot_next, internal, partial, s) != 0)
+                    return set_err(MGP_E_HIP, std::string(who) + ": pass kernel launch failed");
+                MGP_TRY(fetch());
+                if (res_bad()) return set_err(MGP_E_HIP, std::string(who) + ": a community table overflowed");
+                ++passes;
+                const unsigned __int128 b = res_b();
+                const double sc = lv_score(m2, res[1], b, resolution);
+                if (res_moved() > 0 && sc > best) {  // accepted: the new labels and totals are the level's
+                    std::swap(c, next);
+                    std::swap(tot, tot_next);
+                    best = sc, best_i = res[1], best_b = b;
+                    ++accepted;
+                    undone = 0;
+                } else {
+                    ++undone;  // undone: the labels and totals stay as they were
+                }
+            }
+            total_passes += passes;
+            // ---- the non-empty communities, in label order, are the next level's vertices
+            int64_t n2 = 0;
+            if (agg_flag(nl, c, st.flag.as<int32_t>(), s) != 0 ||
+                scan32(st.flag.as<int32_t>(), nl, st.ren.as<int64_t>(), s) != 0 ||
+                agg_map(n0, st.map.as<int32_t>(), c, st.ren.as<int64_t>(), s) != 0)
+                return set_err(MGP_E_HIP, std::string(who) + ": renumbering kernel launch failed");
+            HIP_TRY(hipMemcpyAsync(&n2, st.ren.as<int64_t>() + nl, 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            levels[4 * n_lv + 0] = nl, levels[4 * n_lv + 1] = n2, levels[4 * n_lv + 2] = passes,
+                              levels[4 * n_lv + 3] = accepted;
+            ++n_lv;
+            if (n2 == nl || n2 == 1 || n_lv >= max_levels) break;
+            const int nx = cur ^ 1;
+            int64_t m_next = 0;
+            if (agg_vertices(g[cur], m, nl, (int)n2, c, st.ren.as<int64_t>(), st.flag.as<int32_t>(), tot, self,
+                             st.d[nx].as<uint64_t>(), st.self[nx].as<uint64_t>(), st.cap.as<int64_t>(), s) != 0 ||
+                scan64(st.cap.as<int64_t>(), n2, st.slot.as<int64_t>(), s) != 0 ||
+                agg_insert(g[cur], m, c, st.ren.as<int64_t>(), st.slot.as<int64_t>(), st.tkeys.as<int32_t>(),
+                           st.tvals.as<uint64_t>(), bad, s) != 0 ||
+                agg_rows((int)n2, st.slot.as<int64_t>(), st.tkeys.as<int32_t>(), st.tvals.as<uint64_t>(),
+                         st.deg.as<int32_t>(), nullptr, s) != 0 ||
+                scan32(st.deg.as<int32_t>(), n2, g[nx].off, s) != 0 ||
+                agg_rows((int)n2, st.slot.as<int64_t>(), st.tkeys.as<int32_t>(), st.tvals.as<uint64_t>(), nullptr,
+                         &g[nx], s) != 0)
+                return set_err(MGP_E_HIP, std::string(who) + ": aggregation kernel launch failed");
+            HIP_TRY(hipMemcpyAsync(&m_next, g[nx].off + n2, 8, hipMemcpyDeviceToHost, s));
+            MGP_TRY(fetch());
+            if (res_bad()) return set_err(MGP_E_HIP, std::string(who) + ": a coarse row's table overflowed");
+            cur = nx, nl = (int)n2, m = m_next;
+        }
+        run.stop();
+        std::vector<int32_t> raw(un);
+        HIP_TRY(hipMemcpyAsync(raw.data(), st.map.p, un * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        run.report(who, "levels, passes", n_lv, total_passes);
+        // numbered from 0 by descending size, ties by smallest member
+        const size_t nc = (size_t)levels[4 * (n_lv - 1) + 1];
+        std::vector<int64_t> size(nc, 0), first(nc, -1);
+        for (size_t v = 0; v < un; ++v) {
+            const size_t r = (size_t)raw[v];
+            if (r >= nc) return set_err(MGP_E_HIP, std::string(who) + ": a label out of range");
+            if (size[r]++ == 0) first[r] = (int64_t)v;
+        }
+        std::vector<int32_t> order(nc), rank(nc);
+        for (size_t r = 0; r < nc; ++r) order[r] = (int32_t)r;
+        std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+            return size[a] != size[b] ? size[a] > size[b] : first[a] < first[b];
+        });
+        for (size_t k = 0; k < nc; ++k) rank[(size_t)order[k]] = (int32_t)k;
+        for (size_t v = 0; v < un; ++v) labels[v] = rank[(size_t)raw[v]];
+        *n_communities = (int64_t)nc;
+        *n_levels = n_lv;
+        sums[0] = m2, sums[1] = best_i, sums[2] = (uint64_t)(best_b >> 64), sums[3] = (uint64_t)best_b;
+        *modularity = lv_score(m2, best_i, best_b, resolution) / (double)m2 / (double)m2;
         return (int)MGP_OK;
     });
 }

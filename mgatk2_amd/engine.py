@@ -45,8 +45,8 @@ ABI_SYMBOLS = (
     "mgp_cell_coverage_run", "mgp_position_coverage_run", "mgp_position_depth_hist_run",
     "mgp_position_depth_next_run", "mgp_cell_coverage_rows", "mgp_position_coverage_rows",
     "mgp_position_depth_hist_rows", "mgp_position_depth_next_rows", "mgp_pair_dist", "mgp_hclust_dist", "mgp_hclust",
-    "mgp_knn", "mgp_snn", "mgp_bgzf_inflate", "mgp_inflater_create", "mgp_inflater_destroy", "mgp_inflater_run",
-    "mgp_inflater_host_alloc", "mgp_inflater_host_release", "mgp_inflater_times",
+    "mgp_knn", "mgp_snn", "mgp_louvain", "mgp_bgzf_inflate", "mgp_inflater_create", "mgp_inflater_destroy",
+    "mgp_inflater_run", "mgp_inflater_host_alloc", "mgp_inflater_host_release", "mgp_inflater_times",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -320,6 +320,10 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_hclust": ([C.c_int, vp, i64, i64, vp, vp, vp, vp], C.c_int),
         "mgp_knn": ([C.c_int, vp, i64, i64, i32, vp, vp], C.c_int),
         "mgp_snn": ([C.c_int, vp, i64, i32, i32, i64, C.POINTER(i64), vp, vp, vp], C.c_int),
+        "mgp_louvain": (
+            [C.c_int, i64, i64, vp, vp, vp, C.c_double, i32, i32, vp, C.POINTER(i64), C.POINTER(C.c_double), vp,
+             C.POINTER(i32), vp], C.c_int
+        ),
         "mgp_bgzf_inflate": ([C.c_int, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp], C.c_int),
         "mgp_inflater_create": ([C.c_int, i64, i64, C.POINTER(vp)], C.c_int),
         "mgp_inflater_destroy": ([vp], None),
@@ -416,6 +420,7 @@ class EngineResult:
     variant_seconds: dict | None = None  # enable_variants: run_variants' seconds by pass
     clusters: object | None = None  # cluster_result: the ClusterResult
     neighbors: object | None = None  # neighbor_result: the NeighborGraph
+    clonotypes: object | None = None  # clonotype_result: the Clonotypes
 
     @staticmethod
     def alloc(n_cells: int, L: int, dense: bool = True) -> EngineResult:
@@ -870,6 +875,39 @@ def graph_snn(idx, min_shared: int, device: int = 0):
         order = np.lexsort((out[1], out[0]))
         out = [a[order] for a in out]
     return tuple(out)
+
+
+LOUVAIN_MAX_VERTICES = 1 << 20  # vertices of one mgp_louvain call
+LOUVAIN_MAX_EDGES = 1 << 30     # undirected edges of one call
+LOUVAIN_MAX_WEIGHT = 1 << 20    # an edge's integer weight, in units of 2^-20
+LOUVAIN_MAX_LEVELS = 64         # the cap on max_levels
+LOUVAIN_MAX_PASSES = 1 << 16    # the cap on max_passes
+LOUVAIN_WAVE_ROW = 64           # rows up to here are a wave's (MGP_LOUVAIN_WAVE_ROW lowers it)
+LOUVAIN_LDS_ROW = 2048          # rows up to here use the LDS table (MGP_LOUVAIN_LDS_ROW lowers it)
+
+
+def graph_louvain(n: int, i, j, wq, resolution: float = 1.0, max_levels: int = 32, max_passes: int = 64,
+                  device: int = 0) -> dict:
+    """mgp_louvain: the communities of the graph of n vertices with the undirected edges (i, j),
+    i < j, each pair once, and integer weights wq in 1..2^20 (units of 2^-20). A dict: labels
+    [n] int32 (numbered by descending size, ties by smallest member), n_communities, modularity,
+    m2, internal, b (Python integers) and levels, the (vertices, communities, passes, accepted)
+    of each level. The edges are checked on the device (InvalidInputError)."""
+    i, j, wq = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (i, j, wq))
+    if not i.size == j.size == wq.size:
+        raise InvalidInputError("i, j and wq have one entry per edge")
+    n, ne = int(n), int(i.size)
+    ok = 0 <= n <= LOUVAIN_MAX_VERTICES and 1 <= int(max_levels) <= LOUVAIN_MAX_LEVELS  # (otherwise refused first)
+    labels = np.zeros(n if ok else 0, np.int32)
+    levels = np.zeros((int(max_levels) if ok else 1, 4), np.int64)
+    sums = np.zeros(4, np.uint64)
+    nc, nl, q = C.c_int64(0), C.c_int32(0), C.c_double(0.0)
+    _ck(load_library().mgp_louvain(int(device), n, ne, _ptr(i), _ptr(j), _ptr(wq), float(resolution), int(max_levels),
+                                   int(max_passes), _ptr(labels), C.byref(nc), C.byref(q), _ptr(sums), C.byref(nl),
+                                   _ptr(levels)), "mgp_louvain")
+    return {"labels": labels, "n_communities": int(nc.value), "modularity": float(q.value), "m2": int(sums[0]),
+            "internal": int(sums[1]), "b": (int(sums[2]) << 64) | int(sums[3]),
+            "levels": [tuple(int(x) for x in row) for row in levels[: nl.value]]}
 
 
 INFLATE_MAX_ISIZE = 65536  # inflated bytes of one BGZF block

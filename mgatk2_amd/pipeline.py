@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import gc
 import logging
+import math
 import os
 import threading
 import time
@@ -103,6 +104,8 @@ class MtDNAPipeline:
         clones: int | None = None,
         neighbors: int | None = None,
         snn_prune: float = 1.0 / 15.0,
+        clonotypes: bool = False,
+        clonotype_resolution: float = 1.0,
     ):
         self.bam_path = Path(bam_path)
         # streamed ingest (default; MGP_STREAM=0 decodes the whole chrM set first)
@@ -151,6 +154,17 @@ class MtDNAPipeline:
             raise InvalidInputError(f"neighbors must be in 2..65, got {self.neighbors}")
         if not 0.0 <= self.snn_prune <= 1.0:
             raise InvalidInputError(f"snn_prune must be in [0, 1], got {self.snn_prune}")
+        # the cells' clonotypes, the Louvain communities of the SNN graph (off unless asked for), in variants/
+        self.clonotypes = bool(clonotypes)
+        self.clonotype_resolution = float(clonotype_resolution)
+        if self.clonotypes and self.neighbors is None:
+            raise InvalidInputError("clonotypes needs neighbors (--clonotypes requires --neighbors)")
+        if not (math.isfinite(self.clonotype_resolution) and self.clonotype_resolution > 0.0):
+            raise InvalidInputError("clonotype_resolution must be finite and above 0, got "
+                                    f"{self.clonotype_resolution}")
+        if self.clonotype_resolution != 1.0 and not self.clonotypes:
+            raise InvalidInputError("clonotype_resolution needs clonotypes (--clonotype-resolution requires "
+                                    "--clonotypes)")
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -206,6 +220,8 @@ class MtDNAPipeline:
             processor.enable_clustering(self.clones)
         if self.neighbors is not None:
             processor.enable_neighbors(self.neighbors, self.snn_prune)
+        if self.clonotypes:
+            processor.enable_clonotypes(self.clonotype_resolution)
         if self.stream:
             # one pass: batches decoded on a producer thread, each pushed to the device as
             # it is ready, the windows piled as their reads arrive (readers.py:84-93)
@@ -310,7 +326,17 @@ class MtDNAPipeline:
             if graph.idx is not None:
                 logger.info("Neighbour graph: %d cells, k.param %d, %d SNN edges", graph.n, graph.k_param,
                             int(graph.i.size))
-        t5 = time.time()  # (the clustering's seconds are last_timing["cluster"], the graphs' ["neighbors"])
+            if self.clonotypes:
+                from .analysis.clonotypes import write_clonotype_outputs
+
+                clono = processor.clonotype_result(res)
+                write_clonotype_outputs(clono, af_names, self.output_dir)
+                if clono.result is not None:
+                    logger.info("Clonotypes: %d of %d cells, modularity %.6f (resolution %s, %d levels)",
+                                clono.result.n_communities, clono.n, clono.result.modularity, clono.resolution,
+                                len(clono.result.levels))
+        # (the clustering's seconds are last_timing["cluster"], the graphs' ["neighbors"], the clonotypes' their own)
+        t5 = time.time()
         # streamed: bam_ingest ends with the last decoded batch and `engine` is only what the
         # device still did after it (the rest ran under the decode)
         self.timings = {"bam_ingest": t1 - t0, "engine": t2 - t1, "write": t3 - t2, "report": t4 - t3,
@@ -369,6 +395,8 @@ def run_pipeline(
     clones: int | None = None,
     neighbors: int | None = None,
     snn_prune: float = 1.0 / 15.0,
+    clonotypes: bool = False,
+    clonotype_resolution: float = 1.0,
     device_inflate: bool = False,
 ) -> dict[str, Any]:
     """pipeline.py:183-269. ``min_distance_from_end`` is accepted and, as in the
@@ -385,8 +413,11 @@ def run_pipeline(
     cell tree cut into K clones. ``neighbors`` = K (needs ``call_variants``; Seurat's k.param, 2..65)
     builds the cells' kNN graph over the variants and its SNN graph (Jaccard weights, ``snn_prune``
     as Seurat's prune.SNN) on the device and writes variants/cell_knn.tsv, cell_snn.mtx and
-    cell_snn_barcodes.tsv. ``device_inflate`` inflates the BAM's BGZF blocks on the device (the
-    first of ``devices``) instead of the host pool; the outputs are the same bytes."""
+    cell_snn_barcodes.tsv. ``clonotypes`` (needs ``neighbors``) finds the Louvain communities of that
+    SNN graph on the device, the same on every run (``clonotype_resolution`` as Seurat's resolution),
+    and writes variants/cell_clonotypes.tsv and clonotypes.tsv. ``device_inflate`` inflates the BAM's
+    BGZF blocks on the device (the first of ``devices``) instead of the host pool; the outputs are the
+    same bytes."""
     barcode_metadata = None
     if barcode_file is None:
         from .file_io.barcode_extraction import extract_barcodes_from_bam
@@ -428,6 +459,6 @@ def run_pipeline(
         variant_min_coverage=variant_min_coverage, coverage_stats=coverage_stats,
         cell_min_mean_coverage=cell_min_mean_coverage, cell_min_coverage_breadth=cell_min_coverage_breadth,
         recompute_reference=recompute_reference, cluster=cluster, clones=clones,
-        neighbors=neighbors, snn_prune=snn_prune,
+        neighbors=neighbors, snn_prune=snn_prune, clonotypes=clonotypes, clonotype_resolution=clonotype_resolution,
     )
     return pipeline.run()

@@ -159,6 +159,7 @@ class CellProcessor:
         self.coverage_opt: dict | None = None
         self.cluster_opt: dict | None = None
         self.neighbors_opt: dict | None = None
+        self.clonotypes_opt: dict | None = None
 
     # txt output on the device ----------------------------------------------
     def enable_device_txt(self, prefix, names: list[str]):
@@ -264,6 +265,35 @@ class CellProcessor:
         finally:
             self.last_timing["neighbors"] = time.perf_counter() - t0
         return res.neighbors
+
+    def enable_clonotypes(self, resolution: float = 1.0):
+        """Find the cells' clonotypes, the Louvain communities of the run's SNN graph (mgp_louvain;
+        analysis/clonotypes.py), when clonotype_result is called; needs enable_neighbors.
+        `resolution` is Seurat's."""
+        import math
+
+        if self.neighbors_opt is None:
+            raise InvalidInputError("the clonotypes need the neighbour graph (enable_neighbors first)")
+        if not (math.isfinite(float(resolution)) and float(resolution) > 0.0):
+            raise InvalidInputError(f"the resolution must be finite and above 0, got {resolution}")
+        self.clonotypes_opt = dict(resolution=float(resolution))
+
+    def clonotype_result(self, res: EngineResult):
+        """The clonotypes of a finished run's SNN graph (res.neighbors; neighbor_result first), on
+        the first device, with their mean heteroplasmy and heatmap order from res.allele_freq.
+        Sets res.clonotypes and last_timing["clonotypes"]; returns the Clonotypes (None when not
+        enabled)."""
+        if self.clonotypes_opt is None:
+            return None
+        from ..analysis.clonotypes import find_clonotypes
+
+        t0 = time.perf_counter()
+        try:
+            res.clonotypes = find_clonotypes(res.neighbors, res.allele_freq, table=res.variants,
+                                             device=self.devices[0], **self.clonotypes_opt)
+        finally:
+            self.last_timing["clonotypes"] = time.perf_counter() - t0
+        return res.clonotypes
 
     @staticmethod
     def _population(res: EngineResult) -> np.ndarray:
