@@ -20,6 +20,7 @@ from 1 in the files, as ``cell_clones.tsv`` numbers its clones.
 from __future__ import annotations
 
 import logging
+import math
 import time
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -28,6 +29,7 @@ import numpy as np
 
 from .. import engine as _engine
 from ..exceptions import InvalidInputError
+from .variants import heteroplasmy_matrix, variants_dir
 
 logger = logging.getLogger(__name__)
 
@@ -72,10 +74,16 @@ def _checked_edges(n, i, j, wq):
     return n, i.astype(np.int32), j.astype(np.int32), wq.astype(np.int32)
 
 
-def _checked_options(resolution, max_levels, max_passes):
-    resolution, max_levels, max_passes = float(resolution), int(max_levels), int(max_passes)
-    if not (np.isfinite(resolution) and resolution > 0.0):
+def check_resolution(resolution) -> float:
+    """Seurat's resolution as a float, finite and above 0."""
+    resolution = float(resolution)
+    if not (math.isfinite(resolution) and resolution > 0.0):
         raise InvalidInputError(f"the resolution must be finite and above 0, got {resolution}")
+    return resolution
+
+
+def _checked_options(resolution, max_levels, max_passes):
+    resolution, max_levels, max_passes = check_resolution(resolution), int(max_levels), int(max_passes)
     if not 1 <= max_levels <= MAX_LEVELS:
         raise InvalidInputError(f"max_levels must be in 1..{MAX_LEVELS}, got {max_levels}")
     if not 1 <= max_passes <= MAX_PASSES:
@@ -157,7 +165,7 @@ class Clonotypes:
 def find_clonotypes(neighbor_graph, allele_freq=None, table=None, resolution: float = 1.0, max_levels: int = 32,
                     max_passes: int = 64, device: int = 0) -> Clonotypes:
     """The clonotypes of a NeighborGraph's SNN graph. With `allele_freq` [n_variants, n_cells]
-    (and `table`, whose genomic order the tree's features then take, as in :mod:`.clustering`)
+    (and `table`, whose genomic order the tree's features then take: heteroplasmy_matrix's note)
     also each clonotype's mean heteroplasmy and the clonotypes' heatmap order by the device's
     complete-linkage tree over those means (what FindClonotypes does after clustering; one
     clonotype has rank 1). No graph gives no result (logged)."""
@@ -176,18 +184,14 @@ def find_clonotypes(neighbor_graph, allele_freq=None, table=None, resolution: fl
     sizes = np.bincount(res.labels, minlength=res.n_communities).astype(np.int64)
     mean_af = rank = None
     if allele_freq is not None:
-        af = np.ascontiguousarray(allele_freq, np.float64)
-        if af.ndim != 2 or af.shape[1] != n:
+        af, table, rows = heteroplasmy_matrix(allele_freq, table=table)
+        if af.shape[1] != n:
             raise InvalidInputError(f"the heteroplasmy matrix is [n_variants, {n}]")
-        if table is not None and len(table) != af.shape[0]:
-            raise InvalidInputError(f"{len(table)} variants in the table for {af.shape[0]} rows")
         mean_af = np.zeros((af.shape[0], res.n_communities), np.float64)
         for k in range(res.n_communities):
             mean_af[:, k] = af[:, res.labels == k].mean(axis=1)
-        x = mean_af
-        if hasattr(table, "position") and hasattr(table, "base"):
-            x = mean_af[np.lexsort((np.asarray(table.base), np.asarray(table.position)))]
         if res.n_communities >= 2 and af.shape[0] >= 1:
+            x = mean_af if rows is None else mean_af[rows]
             order = hclust(x=np.ascontiguousarray(x), device=device).order
             rank = np.empty(res.n_communities, np.int32)
             rank[order - 1] = np.arange(1, res.n_communities + 1, dtype=np.int32)
@@ -221,8 +225,7 @@ def write_clonotype_table(clono: Clonotypes, path) -> None:
 def write_clonotype_outputs(clono: Clonotypes, barcodes: list[str], output_dir) -> Path:
     """The clonotypes' files in the run's variants/ directory: cell_clonotypes.tsv and
     clonotypes.tsv. No graph writes nothing."""
-    vdir = Path(output_dir) / "variants"
-    vdir.mkdir(parents=True, exist_ok=True)
+    vdir = variants_dir(output_dir)
     if clono is None or clono.result is None:
         return vdir
     barcodes = list(barcodes)

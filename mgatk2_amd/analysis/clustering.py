@@ -14,13 +14,7 @@ can rebuild an ``hclust`` object from the files and hand it to ``pheatmap(cluste
 Ties go to the smallest i, then the smallest j (R's rule); given the distances, every output
 is exact.
 
-Item numbers. Cells are numbered in the matrix's column order (the run's population). With a
-variant table, variants are numbered in genomic order (position, then base A, C, G, T), not in
-the table's vmr order, and the cells' features are taken in that order too: vmr carries a
-rounding that depends on how the cells were split over device contexts, so its order can differ
-in the last place between two runs on the same reads, and ties between equal rows go to the
-lower item. In genomic order the same reads give the same files however they were sharded. In
-R, ``labels = rownames(allele_freq_mat)[order(position, match(base, c("A", "C", "G", "T")))]``.
+Item numbers (:func:`.variants.heteroplasmy_matrix` has the reason): cells in column order, variants in genomic order.
 """
 
 from __future__ import annotations
@@ -34,6 +28,7 @@ import numpy as np
 
 from .. import engine as _engine
 from ..exceptions import InvalidInputError
+from .variants import heteroplasmy_matrix, variants_dir
 
 logger = logging.getLogger(__name__)
 
@@ -102,50 +97,42 @@ class ClusterResult:
     variant_rows: np.ndarray | None = None  # the matrix row of each variant item (None: item i is row i)
 
 
+def check_clones(clones) -> int | None:
+    """`clones` as cluster_heteroplasmy takes it: None (no cut), or K >= 1 as an int."""
+    if clones is not None and int(clones) < 1:
+        raise InvalidInputError(f"clones must be at least 1, got {clones}")
+    return None if clones is None else int(clones)
+
+
 def cluster_heteroplasmy(result_or_matrix, barcodes=None, table=None, clones: int | None = None,
                          device: int = 0) -> ClusterResult:
     """The two trees of the heteroplasmy matrix [n_variants, n_cells] (a VariantResult, or the
     matrix itself): cells clustered over the variants and variants over the cells, and with
     `clones` = K the cell tree cut into K clones. `barcodes` and `table` (the matrix's column
     and row names), when given, must match its shape; with a VariantTable the variants are
-    numbered in genomic order (the module's note; `variant_rows` is the matrix row of each item),
-    otherwise in row order. A matrix with fewer than 2 cells or fewer
+    numbered in genomic order (heteroplasmy_matrix's note; `variant_rows` is the matrix row of each
+    item), otherwise in row order. A matrix with fewer than 2 cells or fewer
     than 2 variants gives no tree on either side (logged). More than CLUSTER_MAX_ITEMS items
     on a side raise InvalidInputError."""
-    af = getattr(result_or_matrix, "allele_freq", result_or_matrix)
-    if table is None:
-        table = getattr(result_or_matrix, "table", None)
-    if clones is not None and int(clones) < 1:
-        raise InvalidInputError(f"clones must be at least 1, got {clones}")
+    clones = check_clones(clones)
     t0 = time.perf_counter()
-    if af is None:
-        af = np.zeros((0, 0), np.float64)
-    af = np.ascontiguousarray(af, np.float64)
-    if af.ndim != 2:
-        raise InvalidInputError("the heteroplasmy matrix is [n_variants, n_cells]")
+    af, table, rows = heteroplasmy_matrix(result_or_matrix, barcodes, table)
     nv, nc = af.shape
-    if barcodes is not None and len(barcodes) != nc:
-        raise InvalidInputError(f"{len(barcodes)} barcodes for {nc} cells")
-    if table is not None and len(table) != nv:
-        raise InvalidInputError(f"{len(table)} variants in the table for {nv} rows")
     if nv < 2 or nc < 2:
         logger.info("Clustering skipped: %d variants x %d cells (at least 2 of each are needed)", nv, nc)
         return ClusterResult(None, None, None, {"cells": 0.0, "variants": 0.0, "total": time.perf_counter() - t0})
-    if clones is not None and int(clones) > nc:
+    if clones is not None and clones > nc:
         raise InvalidInputError(f"clones must be in 1..{nc} (the cells), got {clones}")
     for side, n in (("cells", nc), ("variants", nv)):
         if n > CLUSTER_MAX_ITEMS:
             raise InvalidInputError(f"clustering: {n} {side}, more than {CLUSTER_MAX_ITEMS} in one call "
                                     "(the distance matrix is 8 n^2 bytes)")
-    rows = None
-    if hasattr(table, "position") and hasattr(table, "base"):
-        rows = np.lexsort((np.asarray(table.base), np.asarray(table.position)))
-        af = np.ascontiguousarray(af[rows])
+    af = af if rows is None else np.ascontiguousarray(af[rows])
     cells = hclust(x=af, device=device)
     t1 = time.perf_counter()
     variants = hclust(x=np.ascontiguousarray(af.T), device=device)
     t2 = time.perf_counter()
-    labels = cells.cutree(int(clones)) if clones is not None else None
+    labels = cells.cutree(clones) if clones is not None else None
     return ClusterResult(cells, variants, labels, {"cells": t1 - t0, "variants": t2 - t1,
                                                    "total": time.perf_counter() - t0}, rows)
 
@@ -193,8 +180,7 @@ def write_cluster_outputs(result: ClusterResult, barcodes: list[str], table, out
     variant_hclust.tsv, variant_order.tsv and, when the cell tree was cut, cell_clones.tsv
     (barcode, clone). A side without a tree writes nothing. `table`: the VariantTable, or the
     variants' names, in the matrix's row order."""
-    vdir = Path(output_dir) / "variants"
-    vdir.mkdir(parents=True, exist_ok=True)
+    vdir = variants_dir(output_dir)
     names = list(getattr(table, "variant", table))
     if result.variant_rows is not None:
         names = [names[int(r)] for r in result.variant_rows]

@@ -15,10 +15,7 @@ weight is Seurat's ``shared / (2K - shared)``, kept when ``weight >= prune``. Th
 integers: ``prune`` becomes the smallest count that passes (:func:`min_shared_for`) and the
 weight is one division here. Every output is unique: the order is strict.
 
-Item numbers. Cells are numbered in the matrix's column order; with a variant table the
-features are taken in genomic order (position, then base A, C, G, T) as in
-:mod:`.clustering` and for the same reason: the sum's order fixes a distance's last bits,
-and the table's vmr order can differ between two shardings of one run.
+Item numbers (:func:`.variants.heteroplasmy_matrix` has the reason): cells in column order, features in genomic order.
 """
 
 from __future__ import annotations
@@ -32,6 +29,7 @@ import numpy as np
 
 from .. import engine as _engine
 from ..exceptions import InvalidInputError
+from .variants import heteroplasmy_matrix, variants_dir
 
 logger = logging.getLogger(__name__)
 
@@ -40,14 +38,29 @@ GRAPH_MAX_K = _engine.GRAPH_MAX_K
 DEFAULT_PRUNE = 1.0 / 15.0  # Seurat's prune.SNN
 
 
+def check_neighbors(neighbors) -> int:
+    """Seurat's k.param (the cell and its K - 1 nearest others) as an int, 2 <= K <= GRAPH_MAX_K + 1."""
+    neighbors = int(neighbors)
+    if not 2 <= neighbors <= GRAPH_MAX_K + 1:
+        raise InvalidInputError(f"neighbors must be in 2..{GRAPH_MAX_K + 1}, got {neighbors}")
+    return neighbors
+
+
+def check_prune(prune) -> float:
+    """Seurat's prune.SNN as a float, 0 <= prune <= 1 (a NaN is refused)."""
+    prune = float(prune)
+    if not 0.0 <= prune <= 1.0:
+        raise InvalidInputError(f"prune must be in [0, 1], got {prune}")
+    return prune
+
+
 def min_shared_for(K: int, prune: float) -> int:
     """The smallest shared count s in 1..K that Seurat's ComputeSNN keeps among sets of K members:
     its own fp64 expression s / (2K - s), kept unless below `prune` (0 <= prune <= 1)."""
-    K, prune = int(K), float(prune)
+    K = int(K)
     if K < 1:
         raise InvalidInputError(f"K must be at least 1, got {K}")
-    if not 0.0 <= prune <= 1.0:
-        raise InvalidInputError(f"prune must be in [0, 1], got {prune}")
+    prune = check_prune(prune)
     for s in range(1, K + 1):
         if not float(s) / float(2 * K - s) < prune:
             return s
@@ -110,27 +123,12 @@ def neighbor_graph(result_or_matrix, barcodes=None, table=None, neighbors: int =
     VariantResult, or the matrix itself). `neighbors` = K is Seurat's k.param (the cell and its
     K - 1 nearest others, 2 <= K <= GRAPH_MAX_K + 1; clipped to the number of cells), `prune` its
     prune.SNN. `barcodes` and `table`, when given, must match the matrix's shape; with a
-    VariantTable the features are taken in genomic order (the module's note). Fewer than 2 cells
+    VariantTable the features are taken in genomic order (heteroplasmy_matrix's note). Fewer than 2 cells
     or no variant give no graph (logged). More than GRAPH_MAX_ITEMS cells raise InvalidInputError."""
-    af = getattr(result_or_matrix, "allele_freq", result_or_matrix)
-    if table is None:
-        table = getattr(result_or_matrix, "table", None)
-    neighbors, prune = int(neighbors), float(prune)
-    if not 2 <= neighbors <= GRAPH_MAX_K + 1:
-        raise InvalidInputError(f"neighbors must be in 2..{GRAPH_MAX_K + 1}, got {neighbors}")
-    if not 0.0 <= prune <= 1.0:
-        raise InvalidInputError(f"prune must be in [0, 1], got {prune}")
+    neighbors, prune = check_neighbors(neighbors), check_prune(prune)
     t0 = time.perf_counter()
-    if af is None:
-        af = np.zeros((0, 0), np.float64)
-    af = np.ascontiguousarray(af, np.float64)
-    if af.ndim != 2:
-        raise InvalidInputError("the heteroplasmy matrix is [n_variants, n_cells]")
+    af, table, rows = heteroplasmy_matrix(result_or_matrix, barcodes, table)
     nv, nc = af.shape
-    if barcodes is not None and len(barcodes) != nc:
-        raise InvalidInputError(f"{len(barcodes)} barcodes for {nc} cells")
-    if table is not None and len(table) != nv:
-        raise InvalidInputError(f"{len(table)} variants in the table for {nv} rows")
     if nv < 1 or nc < 2:
         logger.info("Neighbour graph skipped: %d variants x %d cells (at least 1 variant and 2 cells are needed)",
                     nv, nc)
@@ -138,9 +136,7 @@ def neighbor_graph(result_or_matrix, barcodes=None, table=None, neighbors: int =
                              seconds={"knn": 0.0, "snn": 0.0, "total": time.perf_counter() - t0})
     if nc > GRAPH_MAX_ITEMS:
         raise InvalidInputError(f"neighbour graph: {nc} cells, more than {GRAPH_MAX_ITEMS} in one call")
-    if hasattr(table, "position") and hasattr(table, "base"):
-        af = np.ascontiguousarray(af[np.lexsort((np.asarray(table.base), np.asarray(table.position)))])
-    idx, dist = knn(af, neighbors - 1, device)
+    idx, dist = knn(af if rows is None else af[rows], neighbors - 1, device)
     t1 = time.perf_counter()
     i, j, shared, weight = snn(idx, prune, device)
     t2 = time.perf_counter()
@@ -178,8 +174,7 @@ def write_snn_mtx(graph: NeighborGraph, path) -> None:
 def write_neighbor_outputs(graph: NeighborGraph, barcodes: list[str], output_dir) -> Path:
     """The graphs' files in the run's variants/ directory: cell_knn.tsv, cell_snn.mtx and
     cell_snn_barcodes.tsv (one barcode per line, the matrix's order). No graph writes nothing."""
-    vdir = Path(output_dir) / "variants"
-    vdir.mkdir(parents=True, exist_ok=True)
+    vdir = variants_dir(output_dir)
     if graph is None or graph.idx is None:
         return vdir
     barcodes = list(barcodes)

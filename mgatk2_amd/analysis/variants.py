@@ -241,7 +241,42 @@ def identify_variants(source, ref_alleles: list[str] | None = None, cells=None, 
                         low_coverage_threshold, matrix=False).table
 
 
+# ---- the matrix as the analyses take it ----------------------------------------------
+
+def heteroplasmy_matrix(result_or_matrix, barcodes=None, table=None):
+    """(af, table, rows) for the analyses of the heteroplasmy matrix (a VariantResult, or the matrix itself): af
+    [n_variants, n_cells] contiguous fp64 (None: 0 x 0), `table` or the result's own, `barcodes` and `table` (the
+    column and row names), when given, checked against its shape; rows: its rows in genomic order, or None.
+
+    Item numbers. Cells are numbered in the matrix's column order (the run's population). With a variant table,
+    variants are numbered in genomic order (position, then base A, C, G, T), not in the table's vmr order, and
+    the cells' features are taken in that order too: vmr carries a rounding that depends on how the cells were
+    split over device contexts, so its order can differ in the last place between two runs on the same reads,
+    ties between equal rows go to the lower item, and a sum's order fixes a distance's last bits. In genomic
+    order the same reads give the same files however they were sharded. In R,
+    ``labels = rownames(allele_freq_mat)[order(position, match(base, c("A", "C", "G", "T")))]``."""
+    af = getattr(result_or_matrix, "allele_freq", result_or_matrix)
+    if table is None:
+        table = getattr(result_or_matrix, "table", None)
+    af = np.ascontiguousarray(np.zeros((0, 0)) if af is None else af, np.float64)
+    if af.ndim != 2:
+        raise InvalidInputError("the heteroplasmy matrix is [n_variants, n_cells]")
+    if barcodes is not None and len(barcodes) != af.shape[1]:
+        raise InvalidInputError(f"{len(barcodes)} barcodes for {af.shape[1]} cells")
+    if table is not None and len(table) != af.shape[0]:
+        raise InvalidInputError(f"{len(table)} variants in the table for {af.shape[0]} rows")
+    genomic = hasattr(table, "position") and hasattr(table, "base")
+    return af, table, np.lexsort((np.asarray(table.base), np.asarray(table.position))) if genomic else None
+
+
 # ---- output files --------------------------------------------------------------------
+
+def variants_dir(output_dir) -> Path:
+    """The run's variants/ directory, made if missing."""
+    vdir = Path(output_dir) / "variants"
+    vdir.mkdir(parents=True, exist_ok=True)
+    return vdir
+
 
 def write_variant_stats(table: VariantTable, path) -> None:
     """variant_stats.tsv: a header and one line per variant, floats as repr."""
@@ -297,8 +332,7 @@ def write_variant_outputs(table: VariantTable, af: np.ndarray | None, barcodes: 
                           output_format: str) -> Path:
     """The run's variants/ directory: variant_stats.tsv always, and the matrix (allele_freq.h5
     for hdf5 output, output.allele_freq.txt.gz otherwise) unless the table is empty."""
-    vdir = Path(output_dir) / "variants"
-    vdir.mkdir(parents=True, exist_ok=True)
+    vdir = variants_dir(output_dir)
     write_variant_stats(table, vdir / "variant_stats.tsv")
     if len(table) and af is not None:
         if output_format == "hdf5":

@@ -67,7 +67,7 @@ def _variant_options(f):
                           "variants/{cell,variant}_{hclust,order}.tsv; needs --variants"),
         click.option("--clones", default=None, type=click.IntRange(min=1), metavar="K",
                      help="Cut the cell tree into K clones (variants/cell_clones.tsv); needs --cluster"),
-        click.option("--neighbors", default=None, type=click.IntRange(min=2, max=65), metavar="K",
+        click.option("--neighbors", default=None, type=click.IntRange(min=2, max=65), metavar="K",  # (GRAPH_MAX_K + 1)
                      help="kNN and SNN graphs of the cells by heteroplasmy on the device, K as Seurat's k.param "
                           "(the cell and its K - 1 nearest others): variants/cell_knn.tsv, cell_snn.mtx, "
                           "cell_snn_barcodes.tsv; needs --variants"),
@@ -93,33 +93,24 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
                   variant_low_coverage, variant_min_coverage, coverage_stats=False, cell_min_mean_coverage=0.0,
                   cell_min_coverage_breadth=0.0, recompute_reference=False, cluster=False, clones=None, neighbors=None,
                   snn_prune=None, clonotypes=False, clonotype_resolution=None, device_inflate=False) -> dict:
-    """The options run_pipeline gets beyond the reference's, each only when asked for: the
-    variant options with --variants; the four coverage options with --coverage-stats,
-    otherwise the filter thresholds and --recompute-reference that were given; --cluster and
-    --clones when given (--cluster needs --variants, --clones needs --cluster: a usage error);
-    --neighbors and --snn-prune when given (--neighbors needs --variants, --snn-prune needs
-    --neighbors: a usage error); --clonotypes and --clonotype-resolution when given (--clonotypes
-    needs --neighbors, --clonotype-resolution needs --clonotypes and a finite value above 0: a
-    usage error); --device-inflate when given."""
-    if neighbors is not None and not call_variants:
-        raise click.UsageError("--neighbors requires --variants")
-    if snn_prune is not None and neighbors is None:
-        raise click.UsageError("--snn-prune requires --neighbors")
-    if clonotypes and neighbors is None:
-        raise click.UsageError("--clonotypes requires --neighbors")
-    if clonotype_resolution is not None and not clonotypes:
-        raise click.UsageError("--clonotype-resolution requires --clonotypes")
-    if clonotype_resolution is not None and not (0.0 < float(clonotype_resolution) < float("inf")):
-        raise click.UsageError("--clonotype-resolution must be finite and above 0")
-    if cluster and not call_variants:
-        raise click.UsageError("--cluster requires --variants")
-    if clones is not None and not cluster:
-        raise click.UsageError("--clones requires --cluster")
-    if clones is not None and int(clones) < 1:
-        raise click.UsageError("--clones must be at least 1")
-    out = {}
+    """The options run_pipeline gets beyond the reference's, each only when asked for: the variant
+    options with --variants; the four coverage options with --coverage-stats, otherwise the filter
+    thresholds and --recompute-reference that were given; the analysis options that were given (one
+    that lacks what it needs, options.REQUIRES, or is out of range: a usage error); --device-inflate."""
+    from .options import AnalysisOptions
+
+    opts = AnalysisOptions(call_variants, cluster, clones, neighbors, snn_prune, clonotypes, clonotype_resolution)
+    opts.check(click.UsageError)
+    out = opts.given()
+    if "clonotype_resolution" in out:  # (a plain float to click; the analyses load only now)
+        from .analysis.clonotypes import check_resolution
+
+        try:
+            check_resolution(clonotype_resolution)
+        except InvalidInputError as e:
+            raise click.UsageError(f"--clonotype-resolution: {e}") from None
     if call_variants:
-        out.update(call_variants=call_variants, variant_min_cells=variant_min_cells,
+        out.update(variant_min_cells=variant_min_cells,
                    variant_min_strand_cor=variant_min_strand_cor, variant_min_vmr=variant_min_vmr,
                    variant_stabilize=variant_stabilize, variant_low_coverage=variant_low_coverage,
                    variant_min_coverage=variant_min_coverage)
@@ -130,18 +121,6 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
         out.update(coverage_stats=True, **cov)
     else:
         out.update({k: v for k, v in cov.items() if v})
-    if cluster:
-        out.update(cluster=True)
-        if clones is not None:
-            out.update(clones=int(clones))
-    if neighbors is not None:
-        out.update(neighbors=int(neighbors))
-        if snn_prune is not None:
-            out.update(snn_prune=float(snn_prune))
-    if clonotypes:
-        out.update(clonotypes=True)
-        if clonotype_resolution is not None:
-            out.update(clonotype_resolution=float(clonotype_resolution))
     if device_inflate:
         out.update(device_inflate=True)
     return out

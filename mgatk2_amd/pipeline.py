@@ -23,18 +23,21 @@ from __future__ import annotations
 
 import gc
 import logging
-import math
 import os
 import threading
 import time
 from pathlib import Path
 from typing import Any
 
+from .analysis.clonotypes import check_resolution
+from .analysis.clustering import check_clones
+from .analysis.neighbors import check_neighbors, check_prune
 from .analysis.qc import QCCalculator
 from .bam import BamFile
 from .config import PipelineConfig
 from .exceptions import InvalidInputError
 from .file_io import IncrementalHDF5Writer, IncrementalTextWriter, write_run_summary
+from .options import AnalysisOptions
 from .processing.processors import CellProcessor
 from .processing.readers import MITO_NAMES, BAMReader
 
@@ -135,36 +138,15 @@ class MtDNAPipeline:
                                      recompute_reference=bool(recompute_reference))
         self.coverage_on = (self.coverage_stats or bool(recompute_reference) or cell_min_mean_coverage > 0
                             or cell_min_coverage_breadth > 0)
-        # clustering of the heteroplasmy matrix (off unless asked for): the trees, the heatmap
-        # orders and, with clones = K, the clone labels, in variants/
-        self.cluster = bool(cluster)
-        self.clones = None if clones is None else int(clones)
-        if self.cluster and not self.call_variants:
-            raise InvalidInputError("cluster needs call_variants (--cluster requires --variants)")
-        if self.clones is not None and not self.cluster:
-            raise InvalidInputError("clones needs cluster (--clones requires --cluster)")
-        if self.clones is not None and self.clones < 1:
-            raise InvalidInputError(f"clones must be at least 1, got {self.clones}")
-        # the cells' kNN and SNN graphs of the heteroplasmy matrix (off unless asked for), in variants/
-        self.neighbors = None if neighbors is None else int(neighbors)
-        self.snn_prune = float(snn_prune)
-        if self.neighbors is not None and not self.call_variants:
-            raise InvalidInputError("neighbors needs call_variants (--neighbors requires --variants)")
-        if self.neighbors is not None and not 2 <= self.neighbors <= 65:
-            raise InvalidInputError(f"neighbors must be in 2..65, got {self.neighbors}")
-        if not 0.0 <= self.snn_prune <= 1.0:
-            raise InvalidInputError(f"snn_prune must be in [0, 1], got {self.snn_prune}")
-        # the cells' clonotypes, the Louvain communities of the SNN graph (off unless asked for), in variants/
-        self.clonotypes = bool(clonotypes)
-        self.clonotype_resolution = float(clonotype_resolution)
-        if self.clonotypes and self.neighbors is None:
-            raise InvalidInputError("clonotypes needs neighbors (--clonotypes requires --neighbors)")
-        if not (math.isfinite(self.clonotype_resolution) and self.clonotype_resolution > 0.0):
-            raise InvalidInputError("clonotype_resolution must be finite and above 0, got "
-                                    f"{self.clonotype_resolution}")
-        if self.clonotype_resolution != 1.0 and not self.clonotypes:
-            raise InvalidInputError("clonotype_resolution needs clonotypes (--clonotype-resolution requires "
-                                    "--clonotypes)")
+        # the analyses of the heteroplasmy matrix (analysis/stages.py), each off unless asked for
+        self.cluster, self.clonotypes = bool(cluster), bool(clonotypes)
+        # (a float default cannot say "not given": snn_prune passes without neighbors, a resolution != 1.0 is given)
+        AnalysisOptions(self.call_variants, self.cluster, clones, neighbors, None, self.clonotypes,
+                        None if clonotype_resolution == 1.0 else clonotype_resolution).check(InvalidInputError, True)
+        self.clones = check_clones(clones)
+        self.neighbors = None if neighbors is None else check_neighbors(neighbors)
+        self.snn_prune = check_prune(snn_prune)
+        self.clonotype_resolution = check_resolution(clonotype_resolution)
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -308,34 +290,17 @@ class MtDNAPipeline:
             except Exception as e:
                 logger.warning("Failed to generate HTML report: %s", e)
         t4 = time.time()
-        if self.cluster and res.variants is not None:
-            # last, so that a population above the clustering's bound raises with every other
-            # output written; the run's engine contexts closed long ago
-            from .analysis.clustering import write_cluster_outputs
+        if processor.stage_opt and res.variants is not None:
+            # last, so that a population above an analysis's bound raises with every other output
+            # written; the run's engine contexts closed long ago
+            from .analysis.stages import STAGES
 
-            clusters = processor.cluster_result(res)
-            write_cluster_outputs(clusters, af_names, res.variants, self.output_dir)
-            if clusters.cells is not None:
-                logger.info("Clustered %d cells and %d variants", clusters.cells.n, clusters.variants.n)
-        if self.neighbors is not None and res.variants is not None:
-            # after the clustering, for the same reason
-            from .analysis.neighbors import write_neighbor_outputs
-
-            graph = processor.neighbor_result(res)
-            write_neighbor_outputs(graph, af_names, self.output_dir)
-            if graph.idx is not None:
-                logger.info("Neighbour graph: %d cells, k.param %d, %d SNN edges", graph.n, graph.k_param,
-                            int(graph.i.size))
-            if self.clonotypes:
-                from .analysis.clonotypes import write_clonotype_outputs
-
-                clono = processor.clonotype_result(res)
-                write_clonotype_outputs(clono, af_names, self.output_dir)
-                if clono.result is not None:
-                    logger.info("Clonotypes: %d of %d cells, modularity %.6f (resolution %s, %d levels)",
-                                clono.result.n_communities, clono.n, clono.result.modularity, clono.resolution,
-                                len(clono.result.levels))
-        # (the clustering's seconds are last_timing["cluster"], the graphs' ["neighbors"], the clonotypes' their own)
+            for stage in STAGES.values():
+                result = processor.stage_result(stage.key, res)
+                if result is not None:
+                    stage.write(result, af_names, res.variants, self.output_dir)
+                    if line := stage.log(result):
+                        logger.info(*line)
         t5 = time.time()
         # streamed: bam_ingest ends with the last decoded batch and `engine` is only what the
         # device still did after it (the rest ran under the decode)
@@ -410,7 +375,7 @@ def run_pipeline(
     ``call_variants``) clusters the cells and the variants of the heteroplasmy matrix on the
     device (the vignette's pheatmap step: Euclidean distances, complete linkage) and writes the
     trees and the heatmap orders to variants/; ``clones`` = K (needs ``cluster``) also writes the
-    cell tree cut into K clones. ``neighbors`` = K (needs ``call_variants``; Seurat's k.param, 2..65)
+    cell tree cut into K clones. ``neighbors`` = K (needs ``call_variants``; Seurat's k.param, 2..GRAPH_MAX_K + 1)
     builds the cells' kNN graph over the variants and its SNN graph (Jaccard weights, ``snn_prune``
     as Seurat's prune.SNN) on the device and writes variants/cell_knn.tsv, cell_snn.mtx and
     cell_snn_barcodes.tsv. ``clonotypes`` (needs ``neighbors``) finds the Louvain communities of that

@@ -20,6 +20,7 @@ import logging
 import os
 import threading
 import time
+from functools import partialmethod
 from queue import Queue
 
 import numpy as np
@@ -157,9 +158,7 @@ class CellProcessor:
         self.h5_out = None
         self.variants_opt: dict | None = None
         self.coverage_opt: dict | None = None
-        self.cluster_opt: dict | None = None
-        self.neighbors_opt: dict | None = None
-        self.clonotypes_opt: dict | None = None
+        self.stage_opt: dict[str, dict] = {}  # the analyses turned on (enable), by stage key
 
     # txt output on the device ----------------------------------------------
     def enable_device_txt(self, prefix, names: list[str]):
@@ -208,92 +207,46 @@ class CellProcessor:
         vr = run_variants(parts, ref, cells=pop, **self.variants_opt)
         res.variants, res.allele_freq, res.variant_seconds = vr.table, vr.allele_freq, vr.seconds
 
-    def enable_clustering(self, clones: int | None = None):
-        """Cluster the cells and the variants of the run's heteroplasmy matrix (mgp_hclust;
-        analysis/clustering.py) when cluster_result is called; needs enable_variants. `clones`
-        = K also cuts the cell tree into K clones."""
-        if self.variants_opt is None:
-            raise InvalidInputError("clustering needs the variants (enable_variants first)")
-        if clones is not None and int(clones) < 1:
-            raise InvalidInputError(f"clones must be at least 1, got {clones}")
-        self.cluster_opt = dict(clones=None if clones is None else int(clones))
+    def enable(self, key: str, **options):
+        """Turn on the analysis `key` of the run's heteroplasmy matrix (analysis/stages.py), made by stage_result.
+        The stage it needs must be on and every option passes its analysis's own checker (InvalidInputError)."""
+        from ..analysis.stages import STAGES
 
-    def cluster_result(self, res: EngineResult):
-        """The clustering of a finished run's matrix (res.allele_freq, the host-merged matrix of
-        every part): one call per side on the first device, after the run's engine contexts have
-        closed, so its distance matrix never competes with the run's buffers. Sets res.clusters
-        and last_timing["cluster"]; returns the ClusterResult (None when not enabled)."""
-        if self.cluster_opt is None:
+        stage = STAGES[key]
+        if (self.variants_opt if stage.needs == "variants" else self.stage_opt.get(stage.needs)) is None:
+            raise InvalidInputError(stage.refusal)
+        self.stage_opt[key] = {name: check(options.get(name, default)) for name, default, check in stage.options}
+
+    def stage_result(self, key: str, res: EngineResult):
+        """The analysis `key` of a finished run's matrix (res.allele_freq, host-merged from every part), on
+        the first device, after the run's engine contexts have closed; the stages in their declared order.
+        Sets the stage's field of res and last_timing[key]; returns the result (None when not enabled)."""
+        if key not in self.stage_opt:
             return None
-        from ..analysis.clustering import cluster_heteroplasmy
+        from ..analysis.stages import STAGES
 
         t0 = time.perf_counter()
         try:
-            res.clusters = cluster_heteroplasmy(res.allele_freq, table=res.variants,
-                                                clones=self.cluster_opt["clones"], device=self.devices[0])
+            setattr(res, STAGES[key].field, STAGES[key].compute(res, self.devices[0], **self.stage_opt[key]))
         finally:
-            self.last_timing["cluster"] = time.perf_counter() - t0
-        return res.clusters
+            self.last_timing[key] = time.perf_counter() - t0
+        return getattr(res, STAGES[key].field)
+
+    def enable_clustering(self, clones: int | None = None):
+        self.enable("cluster", clones=clones)
 
     def enable_neighbors(self, neighbors: int = 20, prune: float = 1.0 / 15.0):
-        """Build the cells' kNN and SNN graphs of the run's heteroplasmy matrix (mgp_knn / mgp_snn;
-        analysis/neighbors.py) when neighbor_result is called; needs enable_variants. `neighbors`
-        = K is Seurat's k.param (the cell and its K - 1 nearest others), `prune` its prune.SNN."""
-        from ..analysis.neighbors import GRAPH_MAX_K
-
-        if self.variants_opt is None:
-            raise InvalidInputError("the neighbour graph needs the variants (enable_variants first)")
-        if not 2 <= int(neighbors) <= GRAPH_MAX_K + 1:
-            raise InvalidInputError(f"neighbors must be in 2..{GRAPH_MAX_K + 1}, got {neighbors}")
-        if not 0.0 <= float(prune) <= 1.0:
-            raise InvalidInputError(f"prune must be in [0, 1], got {prune}")
-        self.neighbors_opt = dict(neighbors=int(neighbors), prune=float(prune))
-
-    def neighbor_result(self, res: EngineResult):
-        """The neighbour graphs of a finished run's matrix (res.allele_freq, the host-merged matrix
-        of every part), on the first device, after the run's engine contexts have closed and
-        after the clustering. Sets res.neighbors and last_timing["neighbors"]; returns the
-        NeighborGraph (None when not enabled)."""
-        if self.neighbors_opt is None:
-            return None
-        from ..analysis.neighbors import neighbor_graph
-
-        t0 = time.perf_counter()
-        try:
-            res.neighbors = neighbor_graph(res.allele_freq, table=res.variants, device=self.devices[0],
-                                           **self.neighbors_opt)
-        finally:
-            self.last_timing["neighbors"] = time.perf_counter() - t0
-        return res.neighbors
+        self.enable("neighbors", neighbors=neighbors, prune=prune)
 
     def enable_clonotypes(self, resolution: float = 1.0):
-        """Find the cells' clonotypes, the Louvain communities of the run's SNN graph (mgp_louvain;
-        analysis/clonotypes.py), when clonotype_result is called; needs enable_neighbors.
-        `resolution` is Seurat's."""
-        import math
+        self.enable("clonotypes", resolution=resolution)
 
-        if self.neighbors_opt is None:
-            raise InvalidInputError("the clonotypes need the neighbour graph (enable_neighbors first)")
-        if not (math.isfinite(float(resolution)) and float(resolution) > 0.0):
-            raise InvalidInputError(f"the resolution must be finite and above 0, got {resolution}")
-        self.clonotypes_opt = dict(resolution=float(resolution))
-
-    def clonotype_result(self, res: EngineResult):
-        """The clonotypes of a finished run's SNN graph (res.neighbors; neighbor_result first), on
-        the first device, with their mean heteroplasmy and heatmap order from res.allele_freq.
-        Sets res.clonotypes and last_timing["clonotypes"]; returns the Clonotypes (None when not
-        enabled)."""
-        if self.clonotypes_opt is None:
-            return None
-        from ..analysis.clonotypes import find_clonotypes
-
-        t0 = time.perf_counter()
-        try:
-            res.clonotypes = find_clonotypes(res.neighbors, res.allele_freq, table=res.variants,
-                                             device=self.devices[0], **self.clonotypes_opt)
-        finally:
-            self.last_timing["clonotypes"] = time.perf_counter() - t0
-        return res.clonotypes
+    cluster_result = partialmethod(stage_result, "cluster")
+    neighbor_result = partialmethod(stage_result, "neighbors")
+    clonotype_result = partialmethod(stage_result, "clonotypes")
+    cluster_opt = property(lambda self: self.stage_opt.get("cluster"))
+    neighbors_opt = property(lambda self: self.stage_opt.get("neighbors"))
+    clonotypes_opt = property(lambda self: self.stage_opt.get("clonotypes"))
 
     @staticmethod
     def _population(res: EngineResult) -> np.ndarray:
