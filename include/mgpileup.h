@@ -936,6 +936,71 @@ int  mgp_inflater_times(mgp_inflater *inflater, double *ms3, int64_t *calls, int
 void *mgp_inflater_host_alloc(int64_t bytes);
 void  mgp_inflater_host_release(void *p);
 
+/* ---- A finished run's count files as a context -------------
+ * Replaces read_mgatk_hdf5 (R/mgatk2_functions.R): the 11 u16 datasets of counts.h5 /
+ * metadata.h5 ([mito_len][n_cols], the planes and chunk order of mgp_h5_tiles) become the
+ * 16-bit cell rows every row job reads, so each mgp_*_run job works on a table context as
+ * on a run's, on the stored values min(v, 65535).
+ *
+ * The detached probe of the streaming inflate first, in mgp_bgzf_inflate's shape: stream i is
+ * one whole zlib stream (RFC 1950: CM 8, CINFO <= 7, no preset dictionary, a valid FCHECK; raw
+ * deflate; the Adler-32 of the output, big-endian) src[coff[i], coff[i] + clen[i]) and
+ * inflates to exactly isize[i] < 2^31 bytes at out[out_off[i], ...), one wave per stream
+ * through a ring of 65,536 bytes. status[i]: 0 ok; 1 invalid stream (the header, or as
+ * mgp_bgzf_inflate's 1); 2 more or fewer than isize bytes, or the input ends early (the
+ * trailer included); 3 a well-formed stream whose Adler-32 differs, or bytes after the
+ * trailer. out receives the bytes of the streams with status 0 alone, and the call still
+ * returns 0: the statuses are the result. Refused before any allocation or launch
+ * (MGP_E_INVALID): as mgp_bgzf_inflate, with isize[i] and clen[i] below 2^31. */
+int  mgp_zlib_inflate(int device, const uint8_t *src, int64_t src_bytes, int64_t n_streams,
+                      const uint64_t *coff, const uint32_t *clen, const uint32_t *isize, const uint64_t *out_off,
+                      uint8_t *out, int64_t out_bytes, int32_t *status /* [n_streams] */);
+/* A context of n_cells x mito_len whose three 16-bit planes (counts, tn5, depth: 22 bytes per
+ * cell and position) are allocated and zeroed, with its jobs' buffers; nothing else of a
+ * run's context exists, and mgp_push_batch*, mgp_run, mgp_sync, mgp_fetch*, the rows targets
+ * and the other calls on a run's reads return MGP_E_STATE with a message naming the table.
+ * A failed open leaves nothing allocated. mgp_close frees it. */
+int  mgp_open_table(int hip_device, int32_t n_cells, int32_t mito_len, mgp_ctx **out);
+/* One batch of a load: all 11 planes and all row chunks of the column chunks
+ * [col_chunk_lo, col_chunk_hi). */
+typedef struct mgp_table_chunks {
+    int64_t        n_cols;          /* columns of the datasets                                 */
+    int32_t        chunk_rows, chunk_cols;
+    int32_t        col_chunk_lo, col_chunk_hi;
+    int32_t        first_cell;      /* the table's cell of column col_chunk_lo * chunk_cols    */
+    int32_t        reserved;
+    const uint8_t *src;             /* host: the chunks' bytes, concatenated plane-major, then
+                                       row chunk, then column chunk (mgp_h5_tiles' order)      */
+    int64_t        src_bytes;
+    const int64_t *chunk_bytes;     /* host: [11][row chunks][hi - lo] their sizes             */
+    const uint8_t *raw;             /* host: the same shape; 0 a zlib stream, 1 stored as it is
+                                       (the filter mask says deflate was skipped), 2 not
+                                       allocated (no bytes): zeros                             */
+    int64_t        n_saturated;     /* out: values equal to 65,535 among the batch's           */
+    double         ms[3];           /* out: device milliseconds of H2D, inflate, transpose     */
+} mgp_table_chunks;
+/* H2D from pinned staging, the inflate (one wave per chunk) and, when every chunk inflated,
+ * the transposition of the tiles into cells [first_cell, ...) of the table, edge padding
+ * dropped, on the table's stream; returns when it is done. A chunk that does not inflate to
+ * chunk_rows * chunk_cols * 2 bytes: MGP_E_INVALID naming the first such chunk (plane, row
+ * chunk, column chunk, status as mgp_zlib_inflate's), and the table's rows of the batch stay
+ * as they were (zero). Refused before any allocation or launch (MGP_E_INVALID, each with
+ * its message; mgp_table_check makes the same checks without a context): a null job, a
+ * chunk shape not positive or of 2^31 bytes or more, column chunks outside the datasets',
+ * more than 2^20 chunks, columns outside the table's cells, a null array, a flag above 2,
+ * a size outside [0, 2^31), an absent chunk with bytes, sizes that do not add up to src_bytes. */
+int  mgp_table_load(mgp_ctx *table, mgp_table_chunks *job);
+/* The same batch as inflated tiles from the host (src: [11][row chunks][hi - lo] tiles of
+ * chunk_rows x chunk_cols u16, src_bytes exactly that; chunk_bytes and raw unused): the
+ * transposition alone (ms[1] is 0). */
+int  mgp_table_load_planes(mgp_ctx *table, mgp_table_chunks *job);
+/* The argument checks of mgp_table_load (planes 0) / mgp_table_load_planes (1) for a table of
+ * n_cells x mito_len; no device call. */
+int  mgp_table_check(int32_t n_cells, int32_t mito_len, const mgp_table_chunks *job, int planes);
+/* The load is complete: from here the mgp_*_run jobs serve the table's rows (before it they
+ * return MGP_E_STATE), and further loads are refused. */
+int  mgp_table_ready(mgp_ctx *table);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,9 +37,10 @@ DEDUP_CHOICES = ["alignment_and_fragment_length", "alignment_start", "none"]
 # ---------------------------------------------------------------------------
 # options (options.py:6-306)
 # ---------------------------------------------------------------------------
-def _variant_options(f):
-    """--variants and its thresholds (after every reference option)."""
-    opts = [
+def _analysis_option_list() -> list:
+    """--variants and its thresholds, the coverage options and the analyses of the heteroplasmy
+    matrix: what `run`, `tenx`, `call` and `analyze` share."""
+    return [
         click.option("--variants", "call_variants", is_flag=True,
                      help="Call variants on the device: variants/variant_stats.tsv and the heteroplasmy matrix"),
         click.option("--variant-min-cells", default=5, type=int, show_default=True,
@@ -80,6 +81,19 @@ def _variant_options(f):
         click.option("--clonotype-resolution", default=None, type=float, metavar="R",
                      help="Resolution of the communities, as Seurat's: above 1 more and smaller clonotypes  "
                           "[default: 1.0]; needs --clonotypes"),
+    ]
+
+
+def _analysis_options(f):
+    """The analysis options alone (`analyze`: there is no BAM)."""
+    for o in reversed(_analysis_option_list()):
+        f = o(f)
+    return f
+
+
+def _variant_options(f):
+    """The analysis options (after every reference option) and --device-inflate."""
+    opts = _analysis_option_list() + [
         click.option("--device-inflate", "device_inflate", is_flag=True,
                      help="Inflate the BAM's BGZF blocks on the device (the first of --devices); CRC32 stays on "
                           "the host. Off by default"),
@@ -466,6 +480,35 @@ def call(bam_path, mito_genome, output_dir, ncores, verbose, max_memory, base_qu
                              base_qual, min_mapq, 0, max_strand_bias, min_distance_from_end, dedup_mode, output_format,
                              ncores == 1, dry_run=False, device=device, variant_args=variant_args)
     logger.info("Analysis completed for all %s BAM files", len(bam_files))
+
+
+@cli.command()
+@click.option("--input", "-i", "input_dir", required=True, type=click.Path(exists=True, file_okay=False),
+              help="Output directory of a finished run (holds output/counts.h5 and output/metadata.h5)")
+@click.option("--output", "-o", "output_dir", default=None, type=click.Path(),
+              help="Where coverage/ and variants/ are written  [default: the input directory]")
+@click.option("--barcodes", "-b", "barcode_file", default=None, type=click.Path(exists=True),
+              help="Analyse only the cells whose barcode is in this file (one per line)")
+@click.option("--host-inflate", is_flag=True,
+              help="Inflate the HDF5 chunks with libhdf5 on the host instead of the device (the same results)")
+@click.option("--verbose", "-v", is_flag=True, help="Enable verbose logging")
+@click.option("--device", "device", default=0, type=int, show_default=True, help="HIP device ordinal")
+@_analysis_options
+def analyze(input_dir, output_dir, barcode_file, host_inflate, verbose, device, **analysis_kw):
+    """Run the analyses on the count files of a finished run (no BAM is read)"""
+    args = _variant_args(**analysis_kw)
+    from .pipeline import analyze_outputs
+
+    if verbose:
+        logging.getLogger("mgatk2_amd").setLevel(logging.DEBUG)
+    try:
+        analyze_outputs(input_dir, output_dir, barcodes=barcode_file, device=device, host_inflate=host_inflate, **args)
+    except InvalidInputError as e:
+        logger.error("Input validation failed: %s", e)
+        raise SystemExit(1) from None
+    except ProcessingError as e:
+        logger.error("Processing failed: %s", e)
+        raise SystemExit(1) from None
 
 
 def main():

@@ -180,8 +180,23 @@ struct mgp_ctx {
 
     // the row jobs' buffers (mgp_jobs.hip); freed with the context, on its device (mgp_close)
     RowJobs* jobs = row_jobs_new();
-    ~mgp_ctx() { row_jobs_free(jobs); }
+
+    // a table context (mgp_open_table): only s_comp, the three 16-bit planes, the jobs and the
+    // loader exist; no run is ever made, and the rows are served once mgp_table_ready was called
+    bool table = false, table_ready = false;
+    TableLoad* load = nullptr;
+    ~mgp_ctx() {
+        row_jobs_free(jobs);
+        table_load_free(load);
+    }
 };
+
+// The entry points of a run refuse a table context (its reads, scratch and events do not exist).
+static int not_table(const mgp_ctx* ctx, const char* who) {
+    if (ctx->table)
+        return set_err(MGP_E_STATE, std::string(who) + ": the context is a loaded table (mgp_open_table), it has no run");
+    return MGP_OK;
+}
 
 // ---------------------------------------------------------------------------
 // kernels
@@ -3286,8 +3301,77 @@ int mgp_open(const mgp_config* cfg, int hip_device, mgp_ctx** out) {
     return MGP_OK;
 }
 
+// A table context's device state freed, and the context (mgp_close; a failed mgp_open_table)
+static void table_close(mgp_ctx* ctx) {
+    (void)hipSetDevice(ctx->dev);
+    if (ctx->s_comp) (void)hipStreamSynchronize(ctx->s_comp);
+    for (DevBuf* b : {&ctx->counts16, &ctx->tn5_16, &ctx->depth16}) b->release();
+    table_load_free(ctx->load);  // (its buffers, on this device)
+    ctx->load = nullptr;
+    if (ctx->s_comp) (void)hipStreamDestroy(ctx->s_comp);
+    delete ctx;
+}
+
+int mgp_open_table(int hip_device, int32_t n_cells, int32_t mito_len, mgp_ctx** out) {
+    if (!out) return set_err(MGP_E_INVALID, "mgp_open_table: null out");
+    *out = nullptr;
+    if (mito_len <= 0 || mito_len > (1 << 24)) return set_err(MGP_E_INVALID, "mgp_open_table: mito_len out of range");
+    if (n_cells < 0) return set_err(MGP_E_INVALID, "mgp_open_table: n_cells < 0");
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (hip_device < 0 || hip_device >= ndev)
+        return set_err(MGP_E_INVALID, "mgp_open_table: hip_device " + std::to_string(hip_device) + " not present (" +
+                                          std::to_string(ndev) + " devices)");
+    HIP_TRY(hipSetDevice(hip_device));
+    mgp_ctx* ctx = new mgp_ctx();
+    ctx->table = true;
+    ctx->load = table_load_new();
+    ctx->dev = hip_device;
+    ctx->cfg.mito_len = mito_len;
+    ctx->cfg.n_cells = n_cells;
+    // no (cell, window) of a table is wide: one window over every position, so that each
+    // use of Rows::W / nwin holds with wide == nullptr (p / W == 0 < nwin; the sweeps stage
+    // one flag per cell, the txt writer one per cell)
+    Geom& g = ctx->g;
+    g.L = mito_len;
+    g.G = 8;
+    g.nc = n_cells;
+    g.W = (mito_len + g.G - 1) / g.G * g.G;
+    g.nwin = 1;
+    const size_t n = (size_t)std::max(n_cells, 1) * (size_t)mito_len;
+    int rc = MGP_OK;
+    hipError_t e = hipStreamCreateWithFlags(&ctx->s_comp, hipStreamNonBlocking);
+    if (e != hipSuccess) rc = set_err(MGP_E_HIP, std::string("mgp_open_table: ") + hipGetErrorString(e));
+    if (rc == MGP_OK) rc = ctx->counts16.ensure(n * 16);
+    if (rc == MGP_OK) rc = ctx->tn5_16.ensure(n * 4);
+    if (rc == MGP_OK) rc = ctx->depth16.ensure(n * 2);
+    DevBuf* planes[3] = {&ctx->counts16, &ctx->tn5_16, &ctx->depth16};
+    const size_t plane_bytes[3] = {n * 16, n * 4, n * 2};
+    for (int k = 0; k < 3; ++k)
+        if (rc == MGP_OK && (e = hipMemsetAsync(planes[k]->p, 0, plane_bytes[k], ctx->s_comp)) != hipSuccess)
+            rc = set_err(MGP_E_HIP, std::string("mgp_open_table: ") + hipGetErrorString(e));
+    if (rc == MGP_OK && (e = hipStreamSynchronize(ctx->s_comp)) != hipSuccess)
+        rc = set_err(MGP_E_HIP, std::string("mgp_open_table: ") + hipGetErrorString(e));
+    if (rc != MGP_OK) {
+        table_close(ctx);  // (nothing stays allocated)
+        return rc;
+    }
+    *out = ctx;
+    return MGP_OK;
+}
+
+int mgp_table_ready(mgp_ctx* ctx) {
+    if (!ctx) return set_err(MGP_E_INVALID, "mgp_table_ready: null ctx");
+    if (!ctx->table) return set_err(MGP_E_STATE, "mgp_table_ready: the context is not a table (mgp_open_table)");
+    HIP_TRY(hipSetDevice(ctx->dev));
+    HIP_TRY(hipStreamSynchronize(ctx->s_comp));
+    ctx->table_ready = true;
+    return MGP_OK;
+}
+
 void mgp_close(mgp_ctx* ctx) {
     if (!ctx) return;
+    if (ctx->table) return table_close(ctx);
     (void)hipSetDevice(ctx->dev);
     (void)hipStreamSynchronize(ctx->s_comp);
     (void)hipStreamSynchronize(ctx->s_copy);
@@ -3377,6 +3461,7 @@ static int push_impl(mgp_ctx* ctx, const mgp_batch* b, const uint16_t* bc16, con
 
 int mgp_push_batch(mgp_ctx* ctx, const mgp_batch* b) {
     if (!ctx || !b) return set_err(MGP_E_INVALID, "null ctx/batch");
+    MGP_TRY(not_table(ctx, "mgp_push_batch"));
     if (b->n_reads < 0 || b->payload_bytes < 0) return set_err(MGP_E_INVALID, "negative sizes");
     if (b->n_reads == 0) return MGP_OK;
     if (!b->bc || !b->tlen || !b->flag || !b->mapq || !b->payload) return set_err(MGP_E_INVALID, "null batch array");
@@ -3385,6 +3470,7 @@ int mgp_push_batch(mgp_ctx* ctx, const mgp_batch* b) {
 
 int mgp_push_batch16(mgp_ctx* ctx, const mgp_batch16* b) {
     if (!ctx || !b) return set_err(MGP_E_INVALID, "null ctx/batch");
+    MGP_TRY(not_table(ctx, "mgp_push_batch16"));
     if (b->n_reads < 0 || b->payload_bytes < 0) return set_err(MGP_E_INVALID, "negative sizes");
     if (b->n_reads == 0) return MGP_OK;
     if (!b->bc || !b->abs_tlen || !b->flag || !b->mapq || !b->payload)
@@ -3534,6 +3620,7 @@ static int push_impl(mgp_ctx* ctx, const mgp_batch* b, const uint16_t* bc16, con
 
 int mgp_reset(mgp_ctx* ctx) {
     if (!ctx) return set_err(MGP_E_INVALID, "null ctx");
+    MGP_TRY(not_table(ctx, "mgp_reset"));
     HIP_TRY(hipSetDevice(ctx->dev));
     HIP_TRY(hipStreamSynchronize(ctx->s_copy));
     HIP_TRY(hipStreamSynchronize(ctx->s_comp));
@@ -4127,6 +4214,7 @@ static int stream_segments(mgp_ctx* ctx, int64_t last_start, uint16_t last_flag)
 
 int mgp_run(mgp_ctx* ctx) {
     if (!ctx) return set_err(MGP_E_INVALID, "null ctx");
+    MGP_TRY(not_table(ctx, "mgp_run"));
     HIP_TRY(hipSetDevice(ctx->dev));
     ctx->ran = false;  // (until this run is queued: an error below leaves no results)
     // a run not begun by streaming segments is one resident launch of every window
@@ -4156,6 +4244,7 @@ int mgp_run(mgp_ctx* ctx) {
 
 int mgp_sync(mgp_ctx* ctx) {
     if (!ctx) return set_err(MGP_E_INVALID, "null ctx");
+    MGP_TRY(not_table(ctx, "mgp_sync"));
     if (!ctx->ran) return set_err(MGP_E_STATE, "no run to wait for");
     HIP_TRY(hipSetDevice(ctx->dev));
     HIP_TRY(hipStreamSynchronize(ctx->s_comp));
@@ -4193,6 +4282,7 @@ int mgp_sync(mgp_ctx* ctx) {
 
 int mgp_fetch_cells(mgp_ctx* ctx, int32_t lo, int32_t hi, mgp_result* out) {
     if (!ctx || !out) return set_err(MGP_E_INVALID, "null ctx/out");
+    MGP_TRY(not_table(ctx, "mgp_fetch_cells"));
     if (lo < 0 || hi < lo || hi > ctx->g.nc) return set_err(MGP_E_INVALID, "cell range outside [0, n_cells)");
     MGP_TRY(mgp_sync(ctx));
     const Geom& g = ctx->g;
@@ -4244,6 +4334,7 @@ int mgp_fetch(mgp_ctx* ctx, mgp_result* out) {
 
 int mgp_fetch_rows16(mgp_ctx* ctx, int32_t lo, int32_t hi, mgp_rows16* out) {
     if (!ctx || !out) return set_err(MGP_E_INVALID, "null ctx/out");
+    MGP_TRY(not_table(ctx, "mgp_fetch_rows16"));
     if (lo < 0 || hi < lo || hi > ctx->g.nc) return set_err(MGP_E_INVALID, "cell range outside [0, n_cells)");
     MGP_TRY(mgp_sync(ctx));
     const Geom& g = ctx->g;
@@ -4281,6 +4372,7 @@ static int mapped(void* host, void** dev) {
 
 int mgp_set_rows_target(mgp_ctx* ctx, const mgp_rows16* rows, const mgp_rows8* rows8) {
     if (!ctx) return set_err(MGP_E_INVALID, "null ctx");
+    MGP_TRY(not_table(ctx, "mgp_set_rows_target"));
     // (set during a streaming run: the windows piled so far are copied at once, below;
     // replacing or clearing a target mid-run is not allowed)
     if (ctx->seg_open && (!rows || ctx->rows_on))
@@ -4333,6 +4425,7 @@ int mgp_set_rows16_target(mgp_ctx* ctx, const mgp_rows16* rows) { return mgp_set
 
 int mgp_copy_wait(mgp_ctx* ctx) {
     if (!ctx) return set_err(MGP_E_INVALID, "null ctx");
+    MGP_TRY(not_table(ctx, "mgp_copy_wait"));
     HIP_TRY(hipSetDevice(ctx->dev));
     HIP_TRY(hipEventSynchronize(ctx->ev_copy));
     return MGP_OK;
@@ -4426,6 +4519,7 @@ int mgp_comm_unique_id(uint8_t* out128) {
 
 int mgp_comm_init(mgp_ctx* ctx, const uint8_t* uid128, int nranks, int rank) {
     if (!ctx || !uid128 || nranks < 1 || rank < 0 || rank >= nranks) return set_err(MGP_E_INVALID, "bad comm args");
+    MGP_TRY(not_table(ctx, "mgp_comm_init"));
     HIP_TRY(hipSetDevice(ctx->dev));
     ncclUniqueId id;
     std::memcpy(&id, uid128, 128);
@@ -4443,6 +4537,7 @@ int mgp_comm_init(mgp_ctx* ctx, const uint8_t* uid128, int nranks, int rank) {
 int mgp_download_inputs(mgp_ctx* ctx, int32_t* start, int32_t* bc, int32_t* tlen, uint16_t* flag, uint8_t* mapq,
                         uint32_t* span, uint64_t* rec_off, uint8_t* payload) {
     if (!ctx) return set_err(MGP_E_INVALID, "null ctx");
+    MGP_TRY(not_table(ctx, "mgp_download_inputs"));
     HIP_TRY(hipSetDevice(ctx->dev));
     HIP_TRY(hipStreamSynchronize(ctx->s_copy));
     HIP_TRY(hipStreamSynchronize(ctx->s_comp));
@@ -4468,6 +4563,7 @@ int mgp_synth_fill(void* stream, uint64_t seed, int64_t n, int read_len, int n_c
 
 int mgp_synth_generate(mgp_ctx* ctx, const mgp_synth_params* p) {
     if (!ctx || !p || !p->cell_cdf || !p->ref_codes) return set_err(MGP_E_INVALID, "null synth args");
+    MGP_TRY(not_table(ctx, "mgp_synth_generate"));
     const bool shard = p->cell_hi > p->cell_lo;
     if (shard) {
         if (p->cell_lo < 0 || p->cell_hi > p->n_cells || p->shard_world < 0 ||
@@ -4563,6 +4659,16 @@ int mgp_synth_generate(mgp_ctx* ctx, const mgp_synth_params* p) {
 // ---------------------------------------------------------------------------
 int run_rows(mgp_ctx* ctx, const char* no_run, RunRows* out) {
     if (!ctx) return set_err(MGP_E_INVALID, "null ctx");
+    if (ctx->table) {  // the loaded planes: 16-bit rows alone, no wide window, no u32 rows
+        if (!ctx->table_ready) return set_err(MGP_E_STATE, std::string(no_run) + " (the table is not loaded: mgp_table_ready first)");
+        HIP_TRY(hipSetDevice(ctx->dev));
+        const Geom& g = ctx->g;
+        *out = RunRows{ctx->dev, ctx->s_comp, g.nc,
+                       txtgz::Rows{reinterpret_cast<const uint4*>(ctx->counts16.p), ctx->depth16.as<uint16_t>(), nullptr,
+                                   nullptr, nullptr, g.L, g.W, g.nwin},
+                       qc::Tn5{ctx->tn5_16.as<uint32_t>(), nullptr}, ctx->jobs};
+        return MGP_OK;
+    }
     MGP_TRY(mgp_sync(ctx));
     HIP_TRY(hipSetDevice(ctx->dev));
     if (!ctx->ran) return set_err(MGP_E_STATE, std::string(no_run) + " (mgp_run first)");
@@ -4578,4 +4684,14 @@ int run_rows(mgp_ctx* ctx, const char* no_run, RunRows* out) {
 RowJobs* ctx_jobs(mgp_ctx* ctx, int* device) {
     *device = ctx->dev;
     return ctx->jobs;
+}
+
+int table_planes(mgp_ctx* ctx, const char* who, TablePlanes* out) {
+    if (!ctx) return set_err(MGP_E_INVALID, std::string(who) + ": null ctx");
+    if (!ctx->table) return set_err(MGP_E_STATE, std::string(who) + ": the context is not a table (mgp_open_table)");
+    if (ctx->table_ready) return set_err(MGP_E_STATE, std::string(who) + ": the table is ready, its rows are being read");
+    HIP_TRY(hipSetDevice(ctx->dev));
+    *out = TablePlanes{ctx->dev, ctx->s_comp, ctx->g.nc, ctx->g.L, reinterpret_cast<uint4*>(ctx->counts16.p),
+                       ctx->tn5_16.as<uint32_t>(), ctx->depth16.as<uint16_t>(), ctx->load};
+    return MGP_OK;
 }

@@ -25,6 +25,26 @@
 // or distance code may be incomplete only as one code of one bit; a distance code may be
 // empty (a match then is an error); over-subscribed codes, HLIT > 286 and HDIST > 30 are
 // errors. An unused code decoded from an incomplete set is an error.
+//
+// inflate_zlib (below inflate) is the streaming form for the HDF5 chunks (mgp_table.hip):
+// a whole zlib stream (RFC 1950) of any size below 2^31, its output staged in a ring of
+// kRing bytes and flushed to the caller's bytes half by half, Adler-32 checked. It shares
+// the bit reader, the header parse, the table build and the symbol decode with inflate.
+// Bounds, all explicit:
+//   input   src[i] is read under i < clen: the two header bytes and the four of the trailer
+//           after clen >= 6 / pos + 4 <= clen, the rest through fill_window and the stored
+//           copy as above (over src + 2, clen - 2)
+//   ring    every index is masked with & (kRing - 1); a step writes [op, op + n) with
+//           n <= kHalf - (op - flushed) for a stored piece and n <= 258 for a match, and
+//           op - flushed < kHalf holds before every step, so the bytes written, at most
+//           kHalf + 257 past flushed, never reach the unflushed bytes one turn behind
+//           (flushed + kRing) nor the match sources [op - kHalf, op): dist <= 32768 = kHalf
+//           and dist <= op (the refusal), so a source byte was written by this stream
+//   dst     written only by flush_ring, [flushed, flushed + n) with flushed + n <= op <= isize
+//           (lit: op < isize; copies: len <= isize - op)
+//   loops   the symbol loop on the same budget of 8 * clen + 64 steps; a stored block in
+//           at most 3 pieces (LEN <= 65535 < 2 * kHalf); the Adler sums over a piece of
+//           n <= kHalf bytes: per lane s1 <= 255 * n, s2 <= 255 * n * n < 2^38 in u64
 #pragma once
 #include <stdint.h>
 
@@ -36,9 +56,12 @@
 
 namespace mgp_inflate {
 
-enum : int32_t { ST_OK = 0, ST_INVALID = 1, ST_SIZE = 2 };
+enum : int32_t { ST_OK = 0, ST_INVALID = 1, ST_SIZE = 2, ST_CHECK = 3 };  // (3: inflate_zlib's alone)
 
 constexpr uint32_t kMaxIsize = 65536;
+constexpr uint32_t kRing = 65536, kHalf = 32768;  // inflate_zlib's staging ring and its flush unit
+constexpr uint32_t kAdlerMod = 65521;
+constexpr uint32_t kMaxLanes = 64;  // the widest W (Scratch::red)
 constexpr uint32_t kInWin = 4096;  // bytes of the compressed stream staged at a time
 constexpr uint32_t kLitBits = 10, kDistBits = 8, kClBits = 7;
 constexpr uint32_t kMaxLit = 288, kMaxDist = 32, kMaxCl = 19;
@@ -62,6 +85,7 @@ struct Scratch {
     Huff lit, dist, cl;
     uint8_t lens[kMaxLit + kMaxDist];  // code lengths: literal/length then distance
     uint8_t cl_lens[kMaxCl + 1];
+    uint32_t red[2 * kMaxLanes];  // inflate_zlib: the lanes' Adler-32 sums of a flushed piece
 };
 
 struct HostWave {
@@ -430,6 +454,175 @@ MGPI_HD inline void flush(const W& w, const uint8_t* win, uint32_t n, uint8_t* d
         d32[k] = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
     }
     for (uint32_t i = tail0 + w.lane(); i < n; i += w.width()) dst[i] = win[i];
+}
+
+// The piece ring[(from & mask) ...) of n <= kHalf bytes, which does not wrap (from is a
+// multiple of kHalf), to dst[from, from + n), and its bytes into the Adler-32 state
+// (*a, *b), the same in every lane: lane l sums the bytes i = l, l + width, ... as
+// s1 = sum d_i and s2 = sum (n - i) d_i, the sums are reduced mod 65521 and combined
+// through s->red, and then a' = a + S1, b' = b + n * a + S2 (mod 65521).
+template <class W>
+MGPI_HD inline void flush_ring(const W& w, const uint8_t* ring, uint32_t from, uint32_t n, uint8_t* dst, Scratch* s,
+                               uint32_t* a, uint32_t* b) {
+    if (n == 0) return;
+    w.sync();  // (the piece's bytes are written)
+    const uint8_t* p = ring + (from & (kRing - 1));  // (from & (kRing - 1)) + n <= kRing
+    flush(w, p, n, dst + from);
+    uint64_t s1 = 0, s2 = 0;
+    for (uint32_t i = w.lane(); i < n; i += w.width()) {
+        const uint64_t d = p[i];
+        s1 += d;
+        s2 += (uint64_t)(n - i) * d;
+    }
+    const uint32_t l = w.lane() < kMaxLanes ? w.lane() : kMaxLanes - 1;
+    s->red[2 * l] = (uint32_t)(s1 % kAdlerMod);
+    s->red[2 * l + 1] = (uint32_t)(s2 % kAdlerMod);
+    w.sync();
+    uint64_t t1 = 0, t2 = 0;
+    const uint32_t nl = w.width() < kMaxLanes ? w.width() : kMaxLanes;
+    for (uint32_t k = 0; k < nl; ++k) {
+        t1 += s->red[2 * k];
+        t2 += s->red[2 * k + 1];
+    }
+    const uint64_t a0 = *a;
+    *a = (uint32_t)((a0 + t1) % kAdlerMod);
+    *b = (uint32_t)((*b + (uint64_t)n * a0 + t2) % kAdlerMod);
+    w.sync();  // (red and the piece's ring bytes may be written again)
+}
+
+// Inflates the zlib stream src[0, clen) into dst[0, isize) through ring (kRing bytes).
+// Returns the stream's status, the same in every lane: ST_OK, dst then holds the bytes;
+// ST_INVALID (a bad header or deflate stream), ST_SIZE (more or fewer than isize bytes, or
+// the input ends early), ST_CHECK (a well-formed stream whose Adler-32 differs, or bytes
+// after the trailer). A refused stream may have written a part of dst.
+template <class W>
+MGPI_HD inline int32_t inflate_zlib(const W& w, const uint8_t* src, uint32_t clen, uint8_t* ring, uint8_t* dst,
+                                    uint32_t isize, Scratch* s) {
+    if (isize >= 0x80000000u || clen >= 0x80000000u) return ST_INVALID;
+    if (clen < 2) return ST_SIZE;
+    const uint32_t cmf = src[0], flg = src[1];
+    if ((cmf & 15u) != 8 || (cmf >> 4) > 7 || (flg & 0x20u) || ((cmf << 8) | flg) % 31 != 0) return ST_INVALID;
+    if (clen < 6) return ST_SIZE;
+    Bits b;
+    b.src = src + 2;
+    b.clen = clen - 2;
+    uint32_t op = 0, flushed = 0;  // bytes written to the ring; bytes of them in dst (a multiple of kHalf)
+    uint32_t ad_a = 1, ad_b = 0;
+    uint64_t budget = 8ull * clen + 64;  // steps: block headers and symbols, each takes >= 1 bit
+    bool final_seen = false;
+    while (!final_seen) {
+        if (budget-- == 0) return ST_INVALID;
+        refill(w, b, s);
+        if (b.bitcnt < 3) return ST_SIZE;
+        final_seen = peek(b, 1) != 0;
+        const uint32_t type = peek(b, 3) >> 1;
+        drop(b, 3);
+        if (type == 3) return ST_INVALID;
+        if (type == 0) {
+            drop(b, b.bitcnt & 7);
+            refill(w, b, s);
+            if (b.bitcnt < 32) return ST_SIZE;
+            const uint32_t len = peek(b, 16);
+            drop(b, 16);
+            const uint32_t nlen = peek(b, 16);
+            drop(b, 16);
+            if ((len ^ 0xFFFFu) != nlen) return ST_INVALID;
+            uint32_t pos = b.ip - (b.bitcnt >> 3);    // the byte after NLEN (bitcnt is a multiple of 8)
+            if (len > b.clen - pos) return ST_SIZE;   // (pos <= ip <= clen)
+            if (len > isize - op) return ST_SIZE;     // (op <= isize)
+            for (uint32_t left = len; left;) {        // pieces that end at the half's end at the latest
+                const uint32_t room = kHalf - (op - flushed), n = left < room ? left : room;
+                w.sync();
+                for (uint32_t i = w.lane(); i < n; i += w.width()) ring[(op + i) & (kRing - 1)] = b.src[pos + i];
+                op += n;
+                pos += n;
+                left -= n;
+                if (op - flushed == kHalf) {
+                    flush_ring(w, ring, flushed, kHalf, dst, s, &ad_a, &ad_b);
+                    flushed += kHalf;
+                }
+            }
+            w.sync();
+            b.bitbuf = 0;
+            b.bitcnt = 0;
+            b.ip = pos;
+            b.wbase = b.wend = b.ip;  // (the next refill stages the window from here)
+            continue;
+        }
+        uint32_t nlen = kMaxLit, ndist = kMaxDist;
+        if (type == 1) {
+            fixed_lens(w, s);
+        } else {
+            const int32_t rc = dynamic_header(w, b, s, &nlen, &ndist);
+            if (rc != ST_OK) return rc;
+        }
+        int32_t rc = build(w, s->lens, nlen, kMaxLit, false, &s->lit, s->lit_tab, kLitBits);
+        if (rc != ST_OK) return rc;
+        rc = build(w, s->lens + kMaxLit, ndist, kMaxDist, false, &s->dist, s->dist_tab, kDistBits);
+        if (rc != ST_OK) return rc;
+        bool end_of_block = false;
+        while (!end_of_block) {
+            if (budget-- == 0) return ST_INVALID;
+            refill(w, b, s);
+            uint32_t sym, len;
+            if (decode(b, &s->lit, s->lit_tab, kLitBits, &sym, &len) != ST_OK) return ST_INVALID;
+            if (len > b.bitcnt) return ST_SIZE;
+            drop(b, len);
+            if (sym < 256) {
+                if (op >= isize) return ST_SIZE;
+                if (w.leader()) ring[op & (kRing - 1)] = (uint8_t)sym;
+                ++op;
+            } else if (sym == 256) {
+                end_of_block = true;
+                continue;
+            } else {
+                if (sym >= 286) return ST_INVALID;
+                const uint32_t ls = sym - 257;
+                const uint32_t le = len_extra(ls);
+                if (b.bitcnt < le) return ST_SIZE;
+                const uint32_t mlen = len_base(ls) + peek(b, le);
+                drop(b, le);
+                refill(w, b, s);
+                uint32_t dsym, dlen;
+                if (decode(b, &s->dist, s->dist_tab, kDistBits, &dsym, &dlen) != ST_OK) return ST_INVALID;
+                if (dlen > b.bitcnt) return ST_SIZE;
+                drop(b, dlen);
+                if (dsym >= 30) return ST_INVALID;
+                const uint32_t de = dist_extra(dsym);
+                if (b.bitcnt < de) return ST_SIZE;
+                const uint32_t dist = dist_base(dsym) + peek(b, de);  // <= 32768 = kHalf
+                drop(b, de);
+                if (dist > op) return ST_INVALID;       // before the start of the output
+                if (mlen > isize - op) return ST_SIZE;  // more than isize bytes
+                // every source byte lies in [op - dist, op), still in the ring (dist <= kHalf);
+                // the bytes of an overlapping match (dist < mlen) repeat with period dist
+                w.sync();
+                const uint32_t from = op - dist;
+                if (dist >= mlen) {
+                    for (uint32_t i = w.lane(); i < mlen; i += w.width())
+                        ring[(op + i) & (kRing - 1)] = ring[(from + i) & (kRing - 1)];
+                } else {
+                    for (uint32_t i = w.lane(); i < mlen; i += w.width())
+                        ring[(op + i) & (kRing - 1)] = ring[(from + i % dist) & (kRing - 1)];
+                }
+                w.sync();
+                op += mlen;
+            }
+            if (op - flushed >= kHalf) {  // (< kHalf + 258)
+                flush_ring(w, ring, flushed, kHalf, dst, s, &ad_a, &ad_b);
+                flushed += kHalf;
+            }
+        }
+    }
+    if (op != isize) return ST_SIZE;
+    flush_ring(w, ring, flushed, op - flushed, dst, s, &ad_a, &ad_b);  // the tail, < kHalf bytes
+    // the trailer: Adler-32, big-endian, at the byte after the last block's last bit
+    const uint32_t pos = b.ip - (b.bitcnt >> 3);  // <= b.clen
+    if (b.clen - pos < 4) return ST_SIZE;
+    const uint8_t* t = b.src + pos;
+    const uint32_t want = (uint32_t)t[0] << 24 | (uint32_t)t[1] << 16 | (uint32_t)t[2] << 8 | (uint32_t)t[3];
+    if (want != (ad_b << 16 | ad_a)) return ST_CHECK;
+    return b.clen - pos == 4 ? ST_OK : ST_CHECK;
 }
 
 }  // namespace mgp_inflate

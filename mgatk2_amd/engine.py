@@ -47,6 +47,8 @@ ABI_SYMBOLS = (
     "mgp_position_depth_hist_rows", "mgp_position_depth_next_rows", "mgp_pair_dist", "mgp_hclust_dist", "mgp_hclust",
     "mgp_knn", "mgp_snn", "mgp_louvain", "mgp_bgzf_inflate", "mgp_inflater_create", "mgp_inflater_destroy",
     "mgp_inflater_run", "mgp_inflater_host_alloc", "mgp_inflater_host_release", "mgp_inflater_times",
+    "mgp_zlib_inflate", "mgp_open_table", "mgp_table_load", "mgp_table_load_planes", "mgp_table_check",
+    "mgp_table_ready",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -218,6 +220,27 @@ H5_PLANES = ("A_fwd", "A_rev", "C_fwd", "C_rev", "G_fwd", "G_rev", "T_fwd", "T_r
              "coverage")  # the planes of mgp_h5_tiles, in its order
 
 
+class mgp_table_chunks(C.Structure):
+    _fields_ = [
+        ("n_cols", C.c_int64),
+        ("chunk_rows", C.c_int32),
+        ("chunk_cols", C.c_int32),
+        ("col_chunk_lo", C.c_int32),
+        ("col_chunk_hi", C.c_int32),
+        ("first_cell", C.c_int32),
+        ("reserved", C.c_int32),
+        ("src", C.c_void_p),
+        ("src_bytes", C.c_int64),
+        ("chunk_bytes", C.c_void_p),
+        ("raw", C.c_void_p),
+        ("n_saturated", C.c_int64),
+        ("ms", C.c_double * 3),
+    ]
+
+
+CHUNK_ZLIB, CHUNK_RAW, CHUNK_ABSENT = 0, 1, 2  # mgp_table_chunks.raw
+
+
 class mgp_rows16(C.Structure):
     _fields_ = [
         ("counts", C.c_void_p),
@@ -331,6 +354,12 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_inflater_host_alloc": ([i64], vp),
         "mgp_inflater_host_release": ([vp], None),
         "mgp_inflater_times": ([vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "mgp_zlib_inflate": ([C.c_int, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp], C.c_int),
+        "mgp_open_table": ([C.c_int, i32, i32, C.POINTER(vp)], C.c_int),
+        "mgp_table_load": ([vp, C.POINTER(mgp_table_chunks)], C.c_int),
+        "mgp_table_load_planes": ([vp, C.POINTER(mgp_table_chunks)], C.c_int),
+        "mgp_table_check": ([i32, i32, C.POINTER(mgp_table_chunks), C.c_int], C.c_int),
+        "mgp_table_ready": ([vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -941,6 +970,18 @@ def inflate_bgzf(src, coff, clen, isize, out_off, out: np.ndarray, device: int =
     return status
 
 
+def inflate_zlib(src, coff, clen, isize, out_off, out: np.ndarray, device: int = 0) -> np.ndarray:
+    """mgp_zlib_inflate: stream i is the whole zlib stream src[coff[i], coff[i] + clen[i]) and
+    inflates to isize[i] bytes (any size below 2^31) at out[out_off[i], ...) on the device;
+    returns the streams' statuses (0 ok, 1 invalid stream, 2 wrong size or input ended early,
+    3 Adler-32 differs or bytes follow the trailer). out receives the bytes of the streams with
+    status 0 alone."""
+    args, status, keep = _inflate_args(src, coff, clen, isize, out_off, out)
+    _ck(load_library().mgp_zlib_inflate(int(device), *args), "mgp_zlib_inflate")
+    del keep
+    return status
+
+
 class Inflater:
     """An mgp_inflater: device buffers for max_src_bytes / max_out_bytes per call, a stream
     and pinned staging kept across calls (the BAM ingest's form, BamFile.set_device_inflate)."""
@@ -1005,6 +1046,63 @@ class Engine:
         _ck(self.lib.mgp_open(C.byref(self._c), int(device), C.byref(h)), "mgp_open")
         self._h = h
         self._keep: list = []  # keep host batches alive until the next sync
+
+    # -- a loaded table (mgp_open_table) ------------------------------------
+    @classmethod
+    def open_table(cls, n_cells: int, mito_len: int, device: int = 0) -> Engine:
+        """mgp_open_table: a context of n_cells x mito_len whose 16-bit rows are loaded from a
+        finished run's count files (load / load_planes, then ready) and not made by a run.
+        Every row job (h5_tiles, txt_gz, the coverage and variant passes) then works on it;
+        push, run, sync and fetch are refused. cfg holds n_cells and mito_len alone."""
+        self = cls.__new__(cls)
+        self.lib = load_library()
+        self.cfg = EngineConfig(n_cells=int(n_cells), mito_len=int(mito_len))
+        self._c = None
+        self._keep = []
+        h = C.c_void_p()
+        _ck(self.lib.mgp_open_table(int(device), int(n_cells), int(mito_len), C.byref(h)), "mgp_open_table")
+        self._h = h
+        return self
+
+    def _table_job(self, n_cols, chunks, col_chunks, first_cell, src, chunk_bytes=None, raw=None):
+        src = np.ascontiguousarray(np.frombuffer(src, np.uint8) if isinstance(src, (bytes, bytearray)) else src)
+        src = src.view(np.uint8).reshape(-1)
+        cb = None if chunk_bytes is None else np.ascontiguousarray(chunk_bytes, np.int64)
+        rw = None if raw is None else np.ascontiguousarray(raw, np.uint8)
+        job = mgp_table_chunks(int(n_cols), int(chunks[0]), int(chunks[1]), int(col_chunks[0]), int(col_chunks[1]),
+                               int(first_cell), 0, _ptr(src), int(src.shape[0]), _ptr(cb), _ptr(rw), 0)
+        return job, (src, cb, rw)
+
+    @staticmethod
+    def _table_out(job) -> dict:
+        return {"n_saturated": int(job.n_saturated), "h2d_ms": job.ms[0], "inflate_ms": job.ms[1],
+                "transpose_ms": job.ms[2]}
+
+    def load(self, n_cols: int, chunks: tuple[int, int], col_chunks: tuple[int, int], first_cell: int, src,
+             chunk_bytes, raw) -> dict:
+        """mgp_table_load: the column chunks [col_chunks[0], col_chunks[1]) of the 11 datasets
+        ([mito_len][n_cols], chunk shape `chunks`) into the table's cells from first_cell on.
+        src: the chunks' stored bytes, plane-major (H5_PLANES), then row chunk, then column
+        chunk; chunk_bytes their sizes; raw their kinds (CHUNK_ZLIB, CHUNK_RAW, CHUNK_ABSENT).
+        Returns n_saturated and the device milliseconds of the H2D, the inflate and the
+        transposition."""
+        job, keep = self._table_job(n_cols, chunks, col_chunks, first_cell, src, chunk_bytes, raw)
+        _ck(self.lib.mgp_table_load(self._h, C.byref(job)), "mgp_table_load")
+        del keep
+        return self._table_out(job)
+
+    def load_planes(self, n_cols: int, chunks: tuple[int, int], col_chunks: tuple[int, int], first_cell: int,
+                    tiles) -> dict:
+        """mgp_table_load_planes: the same batch as inflated tiles (u16 [11][row chunks][column
+        chunks][chunk rows][chunk columns], edges padded): the transposition alone."""
+        job, keep = self._table_job(n_cols, chunks, col_chunks, first_cell, tiles)
+        _ck(self.lib.mgp_table_load_planes(self._h, C.byref(job)), "mgp_table_load_planes")
+        del keep
+        return self._table_out(job)
+
+    def ready(self):
+        """mgp_table_ready: the load is complete; the row jobs serve the table from here."""
+        _ck(self.lib.mgp_table_ready(self._h), "mgp_table_ready")
 
     # -- lifecycle ---------------------------------------------------------
     def close(self):

@@ -43,6 +43,8 @@ H5T_CSET_ASCII, H5T_CSET_UTF8 = 0, 1
 H5I_GROUP, H5I_DATASET = 2, 5
 H5_INDEX_NAME, H5_ITER_INC = 0, 0
 H5T_VARIABLE = C.c_size_t(-1).value
+HADDR_UNDEF = C.c_uint64(-1).value
+H5Z_FILTER_DEFLATE = 1
 
 _CANDIDATES = [os.environ.get("MGP_HDF5_LIB"), "/opt/conda/lib/libhdf5.so.103", "/opt/conda/lib/libhdf5.so",
                ctypes.util.find_library("hdf5")]
@@ -110,6 +112,11 @@ def _h5():
         "H5Dget_create_plist": (hid_t, [hid_t]),
         "H5Pget_chunk": (C.c_int, [hid_t, C.c_int, C.POINTER(hsize_t)]),
         "H5Pget_nfilters": (C.c_int, [hid_t]),
+        "H5Pget_filter2": (C.c_int, [hid_t, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_size_t), C.POINTER(C.c_uint),
+                                     C.c_size_t, C.c_char_p, C.POINTER(C.c_uint)]),
+        "H5Dread_chunk": (herr_t, [hid_t, hid_t, C.POINTER(hsize_t), C.POINTER(C.c_uint32), C.c_void_p]),
+        "H5Dget_chunk_info_by_coord": (herr_t, [hid_t, C.POINTER(hsize_t), C.POINTER(C.c_uint), C.POINTER(C.c_uint64),
+                                                C.POINTER(hsize_t)]),
         "H5Gcreate2": (hid_t, [hid_t, C.c_char_p, hid_t, hid_t, hid_t]),
         "H5Gopen2": (hid_t, [hid_t, C.c_char_p, hid_t]),
         "H5Gclose": (herr_t, [hid_t]),
@@ -381,6 +388,58 @@ class Dataset:
             return "gzip" if lib.H5Pget_nfilters(p) > 0 else None
         finally:
             lib.H5Pclose(p)
+
+    @property
+    def filters(self) -> tuple[int, ...]:
+        """The ids of the filter pipeline, in its order (H5Z_FILTER_DEFLATE 1, SHUFFLE 2,
+        FLETCHER32 3, SZIP 4, ...); () for a dataset without filters."""
+        lib = _h5()
+        p = lib.H5Dget_create_plist(self._id)
+        try:
+            out = []
+            for i in range(max(0, lib.H5Pget_nfilters(p))):
+                flags, n, cfg = C.c_uint(), C.c_size_t(0), C.c_uint()
+                out.append(_ck(lib.H5Pget_filter2(p, i, C.byref(flags), C.byref(n), None, 0, None, C.byref(cfg)),
+                               "H5Pget_filter2"))
+            return tuple(out)
+        finally:
+            lib.H5Pclose(p)
+
+    def _chunk_offset(self, coords):
+        ch = self.chunks
+        if ch is None or len(coords) != len(ch):
+            raise ValueError(f"{self.name}: chunk coordinates {tuple(coords)} of a dataset with chunks {ch}")
+        for c, k, n in zip(coords, ch, self.shape):
+            if c < 0 or c * k >= n:
+                raise IndexError(f"{self.name}: chunk {tuple(coords)} outside the dataset")
+        return (hsize_t * len(ch))(*[int(c) * k for c, k in zip(coords, ch)])
+
+    def chunk_info(self, coords):
+        """(stored bytes, filter mask) of the chunk at grid coordinates `coords`; None for a
+        chunk that was never allocated (it reads as the fill value). Bit i of the mask set:
+        filter i of the pipeline was skipped for this chunk."""
+        lib = _h5()
+        off = self._chunk_offset(coords)
+        mask, addr, size = C.c_uint(), C.c_uint64(), hsize_t()
+        _ck(lib.H5Dget_chunk_info_by_coord(self._id, off, C.byref(mask), C.byref(addr), C.byref(size)),
+            "H5Dget_chunk_info_by_coord")
+        if addr.value == HADDR_UNDEF:
+            return None
+        return int(size.value), int(mask.value)
+
+    def read_chunk(self, coords, out) -> int:
+        """H5Dread_chunk: the chunk's bytes as the file stores them (no filter applied) into
+        `out` (a writable u8 array of at least the stored size); returns the filter mask."""
+        lib = _h5()
+        info = self.chunk_info(coords)
+        if info is None:
+            raise KeyError(f"{self.name}: chunk {tuple(coords)} is not allocated")
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable or out.size < info[0]:
+            raise ValueError("out is a writable contiguous uint8 array of at least the chunk's stored size")
+        mask = C.c_uint32()
+        _ck(lib.H5Dread_chunk(self._id, H5P_DEFAULT, self._chunk_offset(coords), C.byref(mask), out.ctypes.data),
+            "H5Dread_chunk")
+        return int(mask.value)
 
     def read(self) -> np.ndarray:
         lib = _h5()

@@ -27,7 +27,10 @@ import os
 import threading
 import time
 from pathlib import Path
+from types import SimpleNamespace
 from typing import Any
+
+import numpy as np
 
 from .analysis.clonotypes import check_resolution
 from .analysis.clustering import check_clones
@@ -72,6 +75,88 @@ class _Background:
         if self._err is not None:
             raise self._err
         return self._out
+
+
+def analysis_settings(call_variants=False, variant_min_cells=5, variant_min_strand_cor=0.65, variant_min_vmr=0.01,
+                      variant_stabilize=False, variant_low_coverage=10, variant_min_coverage=1, coverage_stats=False,
+                      cell_min_mean_coverage=0.0, cell_min_coverage_breadth=0.0, recompute_reference=False,
+                      cluster=False, clones=None, neighbors=None, snn_prune=1.0 / 15.0, clonotypes=False,
+                      clonotype_resolution=1.0) -> dict:
+    """The analysis keywords of run_pipeline / analyze_outputs checked (options.REQUIRES and each
+    analysis's own range, InvalidInputError) and in the form enable_analyses and the writers take."""
+    s: dict[str, Any] = {}
+    # variant calling from the devices' rows (off unless asked for): variants/ in the output
+    s["call_variants"] = bool(call_variants)
+    s["variant_options"] = dict(min_cells=variant_min_cells, min_strand_cor=variant_min_strand_cor,
+                                min_vmr=variant_min_vmr, stabilize_variance=bool(variant_stabilize),
+                                low_coverage_threshold=variant_low_coverage, min_coverage=variant_min_coverage)
+    # coverage QC from the devices' rows (off unless asked for): coverage/ in the output; the
+    # cell filter and the recomputed reference also set the variants' population and reference
+    s["coverage_stats"] = bool(coverage_stats)
+    s["coverage_options"] = dict(min_mean_coverage=float(cell_min_mean_coverage),
+                                 min_coverage_breadth=float(cell_min_coverage_breadth),
+                                 recompute_reference=bool(recompute_reference))
+    s["coverage_on"] = (s["coverage_stats"] or bool(recompute_reference) or cell_min_mean_coverage > 0
+                        or cell_min_coverage_breadth > 0)
+    # the analyses of the heteroplasmy matrix (analysis/stages.py), each off unless asked for
+    s["cluster"], s["clonotypes"] = bool(cluster), bool(clonotypes)
+    # (a float default cannot say "not given": snn_prune passes without neighbors, a resolution != 1.0 is given)
+    AnalysisOptions(s["call_variants"], s["cluster"], clones, neighbors, None, s["clonotypes"],
+                    None if clonotype_resolution == 1.0 else clonotype_resolution).check(InvalidInputError, True)
+    s["clones"] = check_clones(clones)
+    s["neighbors"] = None if neighbors is None else check_neighbors(neighbors)
+    s["snn_prune"] = check_prune(snn_prune)
+    s["clonotype_resolution"] = check_resolution(clonotype_resolution)
+    return s
+
+
+def enable_analyses(processor, s) -> None:
+    """Turn on, on a CellProcessor, the analyses that `s` (an object with analysis_settings' names) asks for."""
+    if s.call_variants:
+        processor.enable_variants(**s.variant_options)
+    if s.coverage_on:
+        processor.enable_coverage(**s.coverage_options)
+    if s.cluster:
+        processor.enable_clustering(s.clones)
+    if s.neighbors is not None:
+        processor.enable_neighbors(s.neighbors, s.snn_prune)
+    if s.clonotypes:
+        processor.enable_clonotypes(s.clonotype_resolution)
+
+
+def write_table_outputs(processor, res, names: list[str], output_dir, output_format: str, coverage_on: bool,
+                        coverage_stats: bool, call_variants: bool) -> list[str]:
+    """coverage/ and variants/ of a result whose population's cells are named `names` (a run's
+    whitelist, a loaded table's columns or subset). Returns the barcodes of the heteroplasmy
+    matrix's columns (the coverage filter's kept cells, if it ran)."""
+    cov = res.coverage if coverage_on else None
+    if cov is not None and (coverage_stats or cov.ref_alleles is not None):
+        from .analysis.coverage import write_coverage_outputs
+
+        write_coverage_outputs(cov, names, output_dir, processor.run_reference(res), tables=coverage_stats)
+        logger.info("%d of %d cells kept by the coverage filter", int(cov.kept.sum()), int(cov.kept.size))
+    af_names = names if res.variant_cells is None else [names[int(i)] for i in res.variant_cells]
+    if call_variants and res.variants is not None:
+        from .analysis.variants import write_variant_outputs
+
+        write_variant_outputs(res.variants, res.allele_freq, af_names, output_dir, output_format)
+        logger.info("%d variants called", len(res.variants))
+    return af_names
+
+
+def write_stage_outputs(processor, res, af_names: list[str], output_dir) -> None:
+    """The analyses of the heteroplasmy matrix that are on (analysis/stages.py), each made and
+    written to variants/ in the declared order."""
+    if not (processor.stage_opt and res.variants is not None):
+        return
+    from .analysis.stages import STAGES
+
+    for stage in STAGES.values():
+        result = processor.stage_result(stage.key, res)
+        if result is not None:
+            stage.write(result, af_names, res.variants, output_dir)
+            if line := stage.log(result):
+                logger.info(*line)
 
 
 class MtDNAPipeline:
@@ -125,28 +210,11 @@ class MtDNAPipeline:
         self.working_directory = working_directory
         self.device = device
         self.devices = list(devices) if devices else [device]
-        # variant calling from the devices' rows (off unless asked for): variants/ in the output
-        self.call_variants = bool(call_variants)
-        self.variant_options = dict(min_cells=variant_min_cells, min_strand_cor=variant_min_strand_cor,
-                                    min_vmr=variant_min_vmr, stabilize_variance=bool(variant_stabilize),
-                                    low_coverage_threshold=variant_low_coverage, min_coverage=variant_min_coverage)
-        # coverage QC from the devices' rows (off unless asked for): coverage/ in the output; the
-        # cell filter and the recomputed reference also set the variants' population and reference
-        self.coverage_stats = bool(coverage_stats)
-        self.coverage_options = dict(min_mean_coverage=float(cell_min_mean_coverage),
-                                     min_coverage_breadth=float(cell_min_coverage_breadth),
-                                     recompute_reference=bool(recompute_reference))
-        self.coverage_on = (self.coverage_stats or bool(recompute_reference) or cell_min_mean_coverage > 0
-                            or cell_min_coverage_breadth > 0)
-        # the analyses of the heteroplasmy matrix (analysis/stages.py), each off unless asked for
-        self.cluster, self.clonotypes = bool(cluster), bool(clonotypes)
-        # (a float default cannot say "not given": snn_prune passes without neighbors, a resolution != 1.0 is given)
-        AnalysisOptions(self.call_variants, self.cluster, clones, neighbors, None, self.clonotypes,
-                        None if clonotype_resolution == 1.0 else clonotype_resolution).check(InvalidInputError, True)
-        self.clones = check_clones(clones)
-        self.neighbors = None if neighbors is None else check_neighbors(neighbors)
-        self.snn_prune = check_prune(snn_prune)
-        self.clonotype_resolution = check_resolution(clonotype_resolution)
+        vars(self).update(analysis_settings(
+            call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
+            variant_low_coverage, variant_min_coverage, coverage_stats, cell_min_mean_coverage,
+            cell_min_coverage_breadth, recompute_reference, cluster, clones, neighbors, snn_prune, clonotypes,
+            clonotype_resolution))
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -194,16 +262,7 @@ class MtDNAPipeline:
         else:
             # the HDF5 chunks are deflated on the device at the end of the run (mgp_h5_tiles)
             processor.enable_device_h5(self.barcode_list)
-        if self.call_variants:
-            processor.enable_variants(**self.variant_options)
-        if self.coverage_on:
-            processor.enable_coverage(**self.coverage_options)
-        if self.cluster:
-            processor.enable_clustering(self.clones)
-        if self.neighbors is not None:
-            processor.enable_neighbors(self.neighbors, self.snn_prune)
-        if self.clonotypes:
-            processor.enable_clonotypes(self.clonotype_resolution)
+        enable_analyses(processor, self)
         if self.stream:
             # one pass: batches decoded on a producer thread, each pushed to the device as
             # it is ready, the windows piled as their reads arrive (readers.py:84-93)
@@ -257,22 +316,8 @@ class MtDNAPipeline:
         meta = QCCalculator(self.config).collect_run_metadata(
             str(self.bam_path), str(self.output_dir), n_cells_input, len(cell_results))
         write_run_summary(meta, qc_dir / "summary.txt")
-        cov = res.coverage if self.coverage_on else None
-        if cov is not None and (self.coverage_stats or cov.ref_alleles is not None):
-            from .analysis.coverage import write_coverage_outputs
-            from .file_io.writers import ref_alleles
-
-            write_coverage_outputs(cov, self.barcode_list, self.output_dir, ref_alleles(res.ref_tally),
-                                   tables=self.coverage_stats)
-            logger.info("%d of %d cells kept by the coverage filter", int(cov.kept.sum()), int(cov.kept.size))
-        # the barcodes of the heteroplasmy matrix's columns (the coverage filter's kept cells, if it ran)
-        af_names = self.barcode_list if res.variant_cells is None else \
-            [self.barcode_list[int(i)] for i in res.variant_cells]
-        if self.call_variants and res.variants is not None:
-            from .analysis.variants import write_variant_outputs
-
-            write_variant_outputs(res.variants, res.allele_freq, af_names, self.output_dir, self.output_format)
-            logger.info("%d variants called", len(res.variants))
+        af_names = write_table_outputs(processor, res, self.barcode_list, self.output_dir, self.output_format,
+                                       self.coverage_on, self.coverage_stats, self.call_variants)
         t3 = time.time()
         gc.collect()
 
@@ -290,17 +335,9 @@ class MtDNAPipeline:
             except Exception as e:
                 logger.warning("Failed to generate HTML report: %s", e)
         t4 = time.time()
-        if processor.stage_opt and res.variants is not None:
-            # last, so that a population above an analysis's bound raises with every other output
-            # written; the run's engine contexts closed long ago
-            from .analysis.stages import STAGES
-
-            for stage in STAGES.values():
-                result = processor.stage_result(stage.key, res)
-                if result is not None:
-                    stage.write(result, af_names, res.variants, self.output_dir)
-                    if line := stage.log(result):
-                        logger.info(*line)
+        # last, so that a population above an analysis's bound raises with every other output
+        # written; the run's engine contexts closed long ago
+        write_stage_outputs(processor, res, af_names, self.output_dir)
         t5 = time.time()
         # streamed: bam_ingest ends with the last decoded batch and `engine` is only what the
         # device still did after it (the rest ran under the decode)
@@ -427,3 +464,67 @@ def run_pipeline(
         neighbors=neighbors, snn_prune=snn_prune, clonotypes=clonotypes, clonotype_resolution=clonotype_resolution,
     )
     return pipeline.run()
+
+
+def _subset_columns(file_barcodes: list[str], barcodes) -> tuple[Any, list[str]]:
+    """subset_mgatk_barcodes (R/mgatk2_functions.R:98-136): the file's columns whose barcode is in
+    `barcodes` (a barcode file or a list), in file order, and their names."""
+    if isinstance(barcodes, (str, os.PathLike)):
+        from .utils import load_barcode_list
+
+        barcodes = load_barcode_list(str(barcodes))
+    want = set(barcodes)
+    keep = [i for i, b in enumerate(file_barcodes) if b in want]
+    missing = sorted(want - set(file_barcodes))
+    if missing:
+        logger.warning("%d of %d barcodes are not in the count files: %s%s", len(missing), len(want),
+                       ", ".join(missing[:5]), ", ..." if len(missing) > 5 else "")
+    if not keep:
+        raise InvalidInputError("No matching barcodes found")
+    logger.info("Found %d matching barcodes (%.1f%%)", len(keep), 100.0 * len(keep) / len(file_barcodes))
+    return np.array(keep, np.int64), [file_barcodes[i] for i in keep]
+
+
+def analyze_outputs(input_dir, output_dir=None, barcodes=None, device: int = 0, host_inflate: bool = False,
+                    **analysis) -> dict[str, Any]:
+    """The analyses of a run (``analysis``: run_pipeline's keywords from call_variants to
+    clonotype_resolution, with its defaults and rules) from the count files a run left in
+    ``input_dir`` (output/counts.h5 and output/metadata.h5, ours or the reference tool's): the
+    R workflow's read_mgatk_hdf5, optionally subset_mgatk_barcodes (``barcodes``: a file or a
+    list; the population is those columns in file order), then the rest, on the device. Every
+    column of the files is a cell, the reference alleles are the files', and the values are
+    the stored min(count, 65535): the results equal R's on the files exactly, and a run's own
+    wherever no count saturates. Writes coverage/ and variants/ into ``output_dir`` (default:
+    ``input_dir``); the count files are never rewritten. ``host_inflate``: libhdf5 inflates
+    the chunks instead of the device (the same results)."""
+    from .engine import EngineResult
+    from .table import load_counts
+
+    s = SimpleNamespace(**analysis_settings(**analysis))
+    t0 = time.time()
+    out_dir = Path(output_dir) if output_dir else Path(input_dir)
+    with load_counts(input_dir, device=device, host_inflate=host_inflate) as loaded:
+        t1 = time.time()
+        n, L = loaded.n_cells, len(loaded.ref_alleles)
+        names, pop = loaded.barcodes, None
+        if barcodes is not None:
+            pop, names = _subset_columns(loaded.barcodes, barcodes)
+        processor = CellProcessor(PipelineConfig(), out_dir, device=device)
+        processor.reference, processor.population = loaded.ref_alleles, pop
+        enable_analyses(processor, s)
+        # the minimal result of a run: every column of the files is a cell that passed
+        res = EngineResult.alloc(n, L, dense=False)
+        res.passed[:] = 1
+        tail = processor._after_run(res, [(loaded.engine, 0, n)] if n else [], writers=False)
+    t2 = time.time()
+    out_dir.mkdir(parents=True, exist_ok=True)
+    af_names = write_table_outputs(processor, res, names, out_dir, "hdf5", s.coverage_on, s.coverage_stats,
+                                   s.call_variants)
+    write_stage_outputs(processor, res, af_names, out_dir)
+    t3 = time.time()
+    timings = {"load": t1 - t0, **{"load_" + k: v for k, v in loaded.seconds.items()}, "analyses": t2 - t1,
+               "write": t3 - t2, "total": t3 - t0, **tail, **processor.last_timing}
+    logger.info("Analyses complete: %d cells of %d columns, load %.2fs, analyses %.2fs, write %.2fs", len(names), n,
+                t1 - t0, t2 - t1, t3 - t2)
+    return {"cells": len(names), "columns": n, "n_saturated": loaded.n_saturated,
+            "variants": None if res.variants is None else len(res.variants), "timings": timings, "result": res}

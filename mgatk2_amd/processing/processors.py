@@ -159,6 +159,10 @@ class CellProcessor:
         self.variants_opt: dict | None = None
         self.coverage_opt: dict | None = None
         self.stage_opt: dict[str, dict] = {}  # the analyses turned on (enable), by stage key
+        # what a loaded table sets (analyze_outputs): the file's reference alleles in place of the
+        # tally's, and the population in place of every cell (a subset of the file's columns)
+        self.reference: list[str] | None = None
+        self.population: np.ndarray | None = None
 
     # txt output on the device ----------------------------------------------
     def enable_device_txt(self, prefix, names: list[str]):
@@ -194,9 +198,8 @@ class CellProcessor:
         """Pass 1 on every part (the devices concurrently), the host merge, pass 2, the
         table, then the matrix of the passing variants, each part filling its own columns."""
         from ..analysis.variants import run_variants
-        from ..file_io.writers import ref_alleles
 
-        pop, ref = self._population(res), ref_alleles(res.ref_tally)
+        pop, ref = self._analysis_population(res), self.run_reference(res)
         cov = res.coverage
         if self.coverage_opt is not None and cov is not None:
             # the vignette's order: the variants of the kept cells, with their own reference
@@ -255,6 +258,15 @@ class CellProcessor:
         n_cells = int(res.passed.shape[0])
         return np.where(res.passed.astype(bool), np.arange(n_cells, dtype=np.int64), -1)
 
+    def _analysis_population(self, res: EngineResult) -> np.ndarray:
+        return self._population(res) if self.population is None else self.population
+
+    def run_reference(self, res: EngineResult) -> list[str]:
+        """The reference alleles the analyses of `res` go by: the tally's, or a loaded table's file's."""
+        from ..file_io.writers import ref_alleles
+
+        return ref_alleles(res.ref_tally) if self.reference is None else list(self.reference)
+
     def enable_coverage(self, min_mean_coverage: float = 0.0, min_coverage_breadth: float = 0.0,
                         recompute_reference: bool = False):
         """Coverage QC from the devices' rows before their contexts close (mgp_cell_coverage_*,
@@ -273,7 +285,7 @@ class CellProcessor:
     def _call_coverage(self, res: EngineResult, parts: DeviceParts) -> None:
         from ..analysis.coverage import run_coverage
 
-        res.coverage = run_coverage(parts, cells=self._population(res), **self.coverage_opt)
+        res.coverage = run_coverage(parts, cells=self._analysis_population(res), **self.coverage_opt)
 
     def _h5_device_on(self) -> bool:
         return self.h5_out is not None and os.environ.get("MGP_H5_DEVICE", "1") != "0"
