@@ -72,7 +72,9 @@ extern "C" {
                                  on the device),
                                  mgp_louvain (Louvain communities of such a graph on the device:
                                  the cells' clonotypes),
-                                 mgp_bgzf_inflate, mgp_inflater_* (BGZF inflate on the device) */
+                                 mgp_bgzf_inflate, mgp_inflater_* (BGZF inflate on the device),
+                                 mgp_group_moments_run, mgp_rows_group_moments (pseudobulk counts
+                                 per cell group on the device) */
 
 /* ---- return codes (0 = success) ------------------------------------------ */
 #define MGP_OK               0
@@ -658,6 +660,33 @@ int  mgp_variant_dev2_rows(int device, const uint32_t *counts, const uint32_t *d
 int  mgp_allele_freq_rows(int device, const uint32_t *counts, const uint32_t *depth, int32_t n_rows,
                           int32_t mito_len, const mgp_variant_job *job, int64_t n_var, const int32_t *pos,
                           const int32_t *base, int32_t min_coverage, double *out);
+/* Pseudobulk counts per cell group on the device (added under ABI 7). What each clone,
+ * clonotype, cell type or donor looks like in bulk, at all mito_len x 4 (position, base)
+ * pairs: the population-wide variant filter cannot see a small group's private variants,
+ * the count rows can. The population is a mgp_variant_job as above (low_coverage_threshold
+ * is not used) and group[k] labels its entry k: 0 .. n_groups - 1, or -1 = in no group
+ * (skipped, never read). Per group, with f, r, cov as above: the sums of f, of r and of
+ * cov, the cells with f + r > 0 and the cells with f >= 2 and r >= 2. One launch covers
+ * every group: the entries are sorted by group and each group's run is cut into items of
+ * at most max_item_cells consecutive entries (0: sized to fill the device), one workgroup
+ * per (256 positions, item). Integer adds only: the same bytes for every max_item_cells.
+ * Bounds: n_groups 1 .. MGP_GROUP_MAX_GROUPS per call (104 bytes x mito_len of device
+ * memory per group), at most 65,536 cells, every f / r count below 2^24; otherwise
+ * MGP_E_INVALID. MGP_E_OOM leaves nothing of the call allocated. */
+#define MGP_GROUP_MAX_GROUPS 256
+typedef struct mgp_group_moments {   /* caller-owned host arrays */
+    uint64_t *fwd, *rev;             /* [n_groups][mito_len][4]: sum of f, of r  */
+    uint64_t *cov;                   /* [n_groups][mito_len]:    sum of cov      */
+    uint32_t *n_det, *n_conf;        /* [n_groups][mito_len][4]                  */
+} mgp_group_moments;
+/* After mgp_run and before mgp_close (implies mgp_sync), or on a ready table context. */
+int  mgp_group_moments_run(mgp_ctx *ctx, const mgp_variant_job *job, const int32_t *group,
+                           int32_t n_groups, int32_t max_item_cells, mgp_group_moments *out);
+/* The same from caller-supplied u32 rows (counts [n_rows][mito_len][8], depth
+ * [n_rows][mito_len]) on `device`, no engine context, as mgp_variant_moments_rows. */
+int  mgp_rows_group_moments(int device, const uint32_t *counts, const uint32_t *depth, int32_t n_rows,
+                            int32_t mito_len, const mgp_variant_job *job, const int32_t *group,
+                            int32_t n_groups, int32_t max_item_cells, mgp_group_moments *out);
 /* Coverage QC on the device (added under ABI 7). Replaces the front half of mgatk's R
  * workflow over counts.h5 (calculate_cell_coverage_stats, calculate_position_coverage_stats,
  * calculate_strand_coverage_stats, calculate_transposition_stats, R/mgatk2_functions.R:138-280):

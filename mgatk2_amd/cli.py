@@ -10,7 +10,8 @@ and ``--cluster`` / ``--clones K`` (the heteroplasmy matrix's cells and variants
 the device, the trees and heatmap orders in variants/), and ``--neighbors K`` / ``--snn-prune P``
 (the cells' kNN and SNN graphs by heteroplasmy on the device, in variants/), and ``--clonotypes`` /
 ``--clonotype-resolution R`` (the Louvain communities of that SNN graph on the device: each cell's
-clonotype, in variants/).
+clonotype, in variants/), and ``--groups FILE`` / ``--group-min-cells N`` / ``--group-min-af F`` (the
+pseudobulk counts and marker variants of every cell group of FILE from the device's rows, groups/).
 Not carried over: ``hardmask-fasta`` (FASTA masking utility, outside the hot path).
 """
 
@@ -84,16 +85,31 @@ def _analysis_option_list() -> list:
     ]
 
 
+def _group_option_list() -> list:
+    """--groups and its thresholds, on `run`, `tenx`, `call` and `analyze`: declared before the shared block."""
+    return [
+        click.option("--groups", "groups", default=None, type=click.Path(exists=True, dir_okay=False), metavar="FILE",
+                     help="Pseudobulk counts and marker variants per cell group on the device (groups/); FILE: "
+                          "barcode<TAB>group lines, e.g. a run's variants/cell_clonotypes.tsv or cell_clones.tsv"),
+        click.option("--group-min-cells", default=None, type=click.IntRange(min=0), metavar="N",
+                     help="Cells of the group with >= 2 reads of the allele on each strand a marker variant needs  "
+                          "[default: 2]; needs --groups"),
+        click.option("--group-min-af", default=None, type=click.FloatRange(min=0.0, max=1.0), metavar="F",
+                     help="Pseudobulk heteroplasmy in the group a marker variant needs  [default: 0.01]; "
+                          "needs --groups"),
+    ]
+
+
 def _analysis_options(f):
-    """The analysis options alone (`analyze`: there is no BAM)."""
-    for o in reversed(_analysis_option_list()):
+    """The group options and the analysis options alone (`analyze`: there is no BAM)."""
+    for o in reversed(_group_option_list() + _analysis_option_list()):
         f = o(f)
     return f
 
 
 def _variant_options(f):
-    """The analysis options (after every reference option) and --device-inflate."""
-    opts = _analysis_option_list() + [
+    """The group options, the analysis options (after every reference option) and --device-inflate."""
+    opts = _group_option_list() + _analysis_option_list() + [
         click.option("--device-inflate", "device_inflate", is_flag=True,
                      help="Inflate the BAM's BGZF blocks on the device (the first of --devices); CRC32 stays on "
                           "the host. Off by default"),
@@ -106,11 +122,13 @@ def _variant_options(f):
 def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
                   variant_low_coverage, variant_min_coverage, coverage_stats=False, cell_min_mean_coverage=0.0,
                   cell_min_coverage_breadth=0.0, recompute_reference=False, cluster=False, clones=None, neighbors=None,
-                  snn_prune=None, clonotypes=False, clonotype_resolution=None, device_inflate=False) -> dict:
+                  snn_prune=None, clonotypes=False, clonotype_resolution=None, device_inflate=False, groups=None,
+                  group_min_cells=None, group_min_af=None) -> dict:
     """The options run_pipeline gets beyond the reference's, each only when asked for: the variant
     options with --variants; the four coverage options with --coverage-stats, otherwise the filter
     thresholds and --recompute-reference that were given; the analysis options that were given (one
-    that lacks what it needs, options.REQUIRES, or is out of range: a usage error); --device-inflate."""
+    that lacks what it needs, options.REQUIRES, or is out of range: a usage error); --device-inflate; --groups
+    and the thresholds given with it (one given without --groups: a usage error)."""
     from .options import AnalysisOptions
 
     opts = AnalysisOptions(call_variants, cluster, clones, neighbors, snn_prune, clonotypes, clonotype_resolution)
@@ -137,6 +155,13 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
         out.update({k: v for k, v in cov.items() if v})
     if device_inflate:
         out.update(device_inflate=True)
+    for flag, value in (("--group-min-cells", group_min_cells), ("--group-min-af", group_min_af)):
+        if value is not None and groups is None:
+            raise click.UsageError(f"{flag} requires --groups")
+    if groups is not None:
+        out.update(groups=str(groups))
+        out.update({k: v for k, v in (("group_min_cells", group_min_cells), ("group_min_af", group_min_af))
+                    if v is not None})
     return out
 
 
@@ -353,6 +378,9 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
         if variant_args and variant_args.get("clonotypes"):
             logger.info("  Clonotypes:             Louvain on the SNN graph, resolution %s",
                         variant_args.get("clonotype_resolution", 1.0))
+        if variant_args and variant_args.get("groups") is not None:
+            logger.info("  Cell groups:            %s, min cells %s, min heteroplasmy %s", variant_args["groups"],
+                        variant_args.get("group_min_cells", 2), variant_args.get("group_min_af", 0.01))
         if variant_args and variant_args.get("device_inflate"):
             logger.info("  BGZF inflate:           on the device")
         if dry_run:
@@ -486,7 +514,7 @@ def call(bam_path, mito_genome, output_dir, ncores, verbose, max_memory, base_qu
 @click.option("--input", "-i", "input_dir", required=True, type=click.Path(exists=True, file_okay=False),
               help="Output directory of a finished run (holds output/counts.h5 and output/metadata.h5)")
 @click.option("--output", "-o", "output_dir", default=None, type=click.Path(),
-              help="Where coverage/ and variants/ are written  [default: the input directory]")
+              help="Where coverage/, variants/ and groups/ are written  [default: the input directory]")
 @click.option("--barcodes", "-b", "barcode_file", default=None, type=click.Path(exists=True),
               help="Analyse only the cells whose barcode is in this file (one per line)")
 @click.option("--host-inflate", is_flag=True,

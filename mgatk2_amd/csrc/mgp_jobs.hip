@@ -1,7 +1,8 @@
 // mgp_jobs.hip — the host drivers of everything that reads a finished run's rows, and
 // their C-ABI entry points (include/mgpileup.h): the txt and HDF5 writers (kernels in
 // mgp_txtgz.hip), the variant statistics (mgp_variants.hip) and the coverage QC passes
-// (mgp_qc.hip). Each job has two forms: *_run on a context's last run, whose rows it gets
+// (mgp_qc.hip), and the pseudobulk counts per cell group (mgp_groups.hip). Each job has two
+// forms: *_run on a context's last run, whose rows it gets
 // through run_rows (mgp_jobs.h: the context itself is opaque here), and the detached
 // *_rows form on u32 rows of the caller's (on_rows). The clustering of the heteroplasmy
 // matrix (mgp_cluster.hip) reads no rows and needs no context: mgp_pair_dist / mgp_hclust*;
@@ -18,6 +19,7 @@
 #include "../../include/mgpileup.h"
 #include "mgp_cluster.h"
 #include "mgp_graph.h"
+#include "mgp_groups.h"
 #include "mgp_host.h"
 #include "mgp_jobs.h"
 #include "mgp_louvain.h"
@@ -46,6 +48,14 @@ struct H5State {
 // mgp_variant_* / mgp_allele_freq_*: the variant reductions' buffers (mgp_variants.hip)
 struct VarState {
     DevBuf cells, acc, part, f64, mu, pos, base, bad, out;
+};
+
+// mgp_group_moments_run / mgp_rows_group_moments: the grouped sweep's buffers (mgp_groups.hip)
+struct GroupState {
+    DevBuf cells, items, acc, bad;
+    void release() {
+        cells.release(), items.release(), acc.release(), bad.release();
+    }
 };
 
 // mgp_cell_coverage_* / mgp_position_*: the coverage QC passes' buffers (mgp_qc.hip)
@@ -77,6 +87,7 @@ struct RowJobs {
     H5State h5;
     VarState var;
     QcState qc;
+    GroupState grp;
 };
 RowJobs* row_jobs_new() { return new RowJobs(); }
 void row_jobs_free(RowJobs* jobs) { delete jobs; }
@@ -660,6 +671,124 @@ int mgp_allele_freq_rows(int device, const uint32_t* counts, const uint32_t* dep
     return on_rows<VarState>(device, "mgp_allele_freq_rows", PL_COUNTS | PL_DEPTH, h,
                              [&](VarState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
         return var_allele_freq(st, s, rows, n_rows, job, n_var, pos, base, min_coverage, out);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// mgp_group_moments_run / mgp_rows_group_moments: pseudobulk counts per cell group
+// ---------------------------------------------------------------------------
+// the pointers, checked before any device call
+static int grp_pointers(const char* who, const mgp_variant_job* job, const int32_t* group,
+                        const mgp_group_moments* out) {
+    if (!job || !group || !out || !out->fwd || !out->rev || !out->cov || !out->n_det || !out->n_conf ||
+        (job->cells && job->n_cells < 0))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    return MGP_OK;
+}
+
+// everything a call is refused for before it allocates or launches
+static int grp_check(const char* who, int32_t n_rows, const mgp_variant_job* job, const int32_t* group,
+                     int32_t n_groups, int32_t max_item_cells, const mgp_group_moments* out) {
+    MGP_TRY(grp_pointers(who, job, group, out));
+    if (n_groups < 1 || n_groups > groups::kMaxGroups)
+        return set_err(MGP_E_INVALID, std::string(who) + ": n_groups must be 1.." + std::to_string(groups::kMaxGroups) +
+                                          " in one call; split the groups");
+    if (max_item_cells < 0) return set_err(MGP_E_INVALID, std::string(who) + ": max_item_cells is negative");
+    const int64_t n = job->cells ? job->n_cells : (int64_t)n_rows;
+    if (n > variants::kMaxCells)
+        return set_err(MGP_E_INVALID, std::string(who) + ": more than 65536 cells in one call (the exactness bound of "
+                                                         "the u64 sums); split the population and add the results");
+    for (int64_t k = 0; k < n; ++k) {
+        if (group[k] < -1 || group[k] >= n_groups)
+            return set_err(MGP_E_INVALID, std::string(who) + ": group label out of range");
+        if (job->cells && (job->cells[k] < -1 || job->cells[k] >= n_rows))
+            return set_err(MGP_E_INVALID, std::string(who) + ": cell out of range");
+    }
+    return MGP_OK;
+}
+
+// (after grp_check)
+static int grp_moments(GroupState& st, hipStream_t s, const txtgz::Rows& rows, int32_t n_rows, const char* who,
+                       const mgp_variant_job* job, const int32_t* group, int32_t n_groups, int32_t max_item_cells,
+                       mgp_group_moments* out) {
+    using namespace groups;
+    const int64_t n = job->cells ? job->n_cells : (int64_t)n_rows;
+    // the population sorted by group (a counting sort: stable), the unlabelled entries left out
+    std::vector<int64_t> start((size_t)n_groups + 1, 0);
+    for (int64_t k = 0; k < n; ++k)
+        if (group[k] >= 0) ++start[(size_t)group[k] + 1];
+    for (int32_t g = 0; g < n_groups; ++g) start[(size_t)g + 1] += start[(size_t)g];
+    const int64_t n_lab = start[(size_t)n_groups];
+    std::vector<int32_t> sorted((size_t)n_lab);
+    {
+        std::vector<int64_t> at(start.begin(), start.end() - 1);
+        for (int64_t k = 0; k < n; ++k)
+            if (group[k] >= 0) sorted[(size_t)at[(size_t)group[k]]++] = job->cells ? job->cells[k] : (int32_t)k;
+    }
+    const int64_t cap = max_item_cells > 0 ? max_item_cells : item_cells(n_lab, rows.L);
+    std::vector<Item> items;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int64_t a = start[(size_t)g], b = start[(size_t)g + 1];
+        for (int64_t k = a; k < b; k += cap)
+            items.push_back(Item{(int32_t)k, (int32_t)std::min(b, k + cap), g, b - a <= cap ? 1 : 0});
+    }
+    const size_t L = (size_t)rows.L, gl = (size_t)n_groups * L;
+    int rc = st.acc.ensure(acc_bytes(n_groups, rows.L));
+    if (rc == MGP_OK) rc = st.cells.ensure((size_t)std::max<int64_t>(n_lab, 1) * 4);
+    if (rc == MGP_OK) rc = st.items.ensure(std::max<size_t>(items.size(), 1) * sizeof(Item));
+    if (rc == MGP_OK) rc = st.bad.ensure(4);
+    if (rc != MGP_OK) {
+        st.release();
+        return rc;
+    }
+    const Acc acc = acc_of(st.acc.p, n_groups, rows.L);
+    HIP_TRY(hipMemsetAsync(st.acc.p, 0, acc_bytes(n_groups, rows.L), s));
+    HIP_TRY(hipMemsetAsync(st.bad.p, 0, 4, s));
+    VarProf prof(s);
+    if (!items.empty()) {
+        HIP_TRY(hipMemcpyAsync(st.cells.p, sorted.data(), (size_t)n_lab * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(st.items.p, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice, s));
+        if (moments(rows, st.cells.as<int32_t>(), st.items.as<Item>(), (int64_t)items.size(), acc, st.bad.as<uint32_t>(),
+                    s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    }
+    prof.stop();
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    prof.report(who, "cells x groups", n_lab, n_groups);
+    if (bad)
+        return set_err(MGP_E_INVALID, std::string(who) + ": a fwd or rev count of the population is 2^24 or more "
+                                                         "(the exactness bound of the u64 sums)");
+    HIP_TRY(hipMemcpyAsync(out->fwd, acc.fwd, gl * 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->rev, acc.rev, gl * 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->cov, acc.cov, gl * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->n_det, acc.n_det, gl * 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->n_conf, acc.n_conf, gl * 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MGP_OK;
+}
+
+int mgp_group_moments_run(mgp_ctx* ctx, const mgp_variant_job* job, const int32_t* group, int32_t n_groups,
+                          int32_t max_item_cells, mgp_group_moments* out) {
+    const char* who = "mgp_group_moments_run";
+    if (!ctx) return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    MGP_TRY(grp_pointers(who, job, group, out));
+    RunRows r;
+    MGP_TRY(run_rows(ctx, "mgp_group_moments_run: no run to read", &r));
+    MGP_TRY(grp_check(who, r.n_cells, job, group, n_groups, max_item_cells, out));
+    return grp_moments(r.jobs->grp, r.stream, r.rows, r.n_cells, who, job, group, n_groups, max_item_cells, out);
+}
+
+int mgp_rows_group_moments(int device, const uint32_t* counts, const uint32_t* depth, int32_t n_rows, int32_t mito_len,
+                           const mgp_variant_job* job, const int32_t* group, int32_t n_groups, int32_t max_item_cells,
+                           mgp_group_moments* out) {
+    const char* who = "mgp_rows_group_moments";
+    MGP_TRY(grp_check(who, n_rows, job, group, n_groups, max_item_cells, out));
+    const HostRows h{counts, nullptr, depth, n_rows, mito_len};
+    return on_rows<GroupState>(device, who, PL_COUNTS | PL_DEPTH, h,
+                               [&](GroupState& st, hipStream_t s, const txtgz::Rows& rows, const qc::Tn5&) {
+        return grp_moments(st, s, rows, n_rows, who, job, group, n_groups, max_item_cells, out);
     });
 }
 

@@ -48,7 +48,7 @@ ABI_SYMBOLS = (
     "mgp_knn", "mgp_snn", "mgp_louvain", "mgp_bgzf_inflate", "mgp_inflater_create", "mgp_inflater_destroy",
     "mgp_inflater_run", "mgp_inflater_host_alloc", "mgp_inflater_host_release", "mgp_inflater_times",
     "mgp_zlib_inflate", "mgp_open_table", "mgp_table_load", "mgp_table_load_planes", "mgp_table_check",
-    "mgp_table_ready",
+    "mgp_table_ready", "mgp_group_moments_run", "mgp_rows_group_moments",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -197,6 +197,15 @@ class mgp_variant_moments(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in MOMENT_FIELDS]
 
 
+# the arrays of mgp_group_moments, in its order, with their dtypes: [n_groups, L, 4] except cov ([n_groups, L])
+GROUP_FIELDS = (("fwd", np.uint64), ("rev", np.uint64), ("cov", np.uint64), ("n_det", np.uint32), ("n_conf", np.uint32))
+GROUP_MAX_GROUPS = 256  # groups of one mgp_group_moments call (MGP_GROUP_MAX_GROUPS)
+
+
+class mgp_group_moments(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _ in GROUP_FIELDS]
+
+
 # the arrays of mgp_cell_coverage ([n_cells]) and mgp_position_coverage ([L]; tally [L, 4]),
 # in their order, with their dtypes
 CELL_COVERAGE_FIELDS = (("s_depth", np.uint64), ("s_depth2", np.uint64), ("max_depth", np.uint32),
@@ -326,6 +335,12 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_allele_freq_rows": (
             [C.c_int, vp, vp, i32, i32, C.POINTER(mgp_variant_job), i64, vp, vp, i32, vp], C.c_int
         ),
+        "mgp_group_moments_run": (
+            [vp, C.POINTER(mgp_variant_job), vp, i32, i32, C.POINTER(mgp_group_moments)], C.c_int
+        ),
+        "mgp_rows_group_moments": (
+            [C.c_int, vp, vp, i32, i32, C.POINTER(mgp_variant_job), vp, i32, i32, C.POINTER(mgp_group_moments)], C.c_int
+        ),
         "mgp_cell_coverage_run": ([vp, C.POINTER(mgp_variant_job), C.POINTER(mgp_cell_coverage)], C.c_int),
         "mgp_position_coverage_run": ([vp, C.POINTER(mgp_variant_job), C.POINTER(mgp_position_coverage)], C.c_int),
         "mgp_position_depth_hist_run": ([vp, C.POINTER(mgp_variant_job), i32, vp, vp], C.c_int),
@@ -450,6 +465,7 @@ class EngineResult:
     clusters: object | None = None  # cluster_result: the ClusterResult
     neighbors: object | None = None  # neighbor_result: the NeighborGraph
     clonotypes: object | None = None  # clonotype_result: the Clonotypes
+    groups: object | None = None  # enable_groups: the GroupResult (analysis/groups.py)
 
     @staticmethod
     def alloc(n_cells: int, L: int, dense: bool = True) -> EngineResult:
@@ -738,6 +754,55 @@ def allele_freq_rows(counts: np.ndarray, depth: np.ndarray, variants, cells=None
                      device: int = 0) -> np.ndarray:
     """mgp_allele_freq_rows: Engine.allele_freq on caller-supplied u32 rows."""
     return _rows_calls(counts, depth, device)[2](variants, cells, min_coverage)
+
+
+def alloc_group_moments(n_groups: int, L: int) -> dict:
+    """Zeroed host arrays of mgp_group_moments for n_groups groups, by field name (GROUP_FIELDS)."""
+    return {k: np.zeros((n_groups, L) if k == "cov" else (n_groups, L, 4), dt) for k, dt in GROUP_FIELDS}
+
+
+def _group_calls(call, n_rows: int, L: int, group, n_groups: int, cells, max_item_cells: int) -> dict:
+    """mgp_group_moments over one row source, call(job, group, n_groups, max_item_cells, out): any n_groups >= 1,
+    in calls of at most GROUP_MAX_GROUPS groups, each with the other calls' labels set to -1 (it sweeps its own
+    cells only), the results concatenated."""
+    job, keep = _variant_job(cells)
+    group = np.ascontiguousarray(group, np.int32)
+    n = n_rows if keep is None else keep.shape[0]
+    n_groups = int(n_groups)
+    if group.shape != (n,):
+        raise InvalidInputError(f"group_moments: {group.shape[0] if group.ndim == 1 else group.shape} labels for "
+                                f"{n} cells")
+    out = alloc_group_moments(max(n_groups, 0), L)
+    if n_groups <= GROUP_MAX_GROUPS:  # one call, the library's own checks
+        call(C.byref(job), _ptr(group), n_groups, int(max_item_cells),
+             C.byref(mgp_group_moments(*[_ptr(out[k]) for k, _ in GROUP_FIELDS])))
+        return out
+    if group.size and (int(group.min()) < -1 or int(group.max()) >= n_groups):
+        raise InvalidInputError("group_moments: group label out of range")
+    for g0 in range(0, n_groups, GROUP_MAX_GROUPS):
+        g1 = min(n_groups, g0 + GROUP_MAX_GROUPS)
+        lab = np.where((group >= g0) & (group < g1), group - g0, -1).astype(np.int32)
+        part = mgp_group_moments(*[_ptr(out[k][g0:g1]) for k, _ in GROUP_FIELDS])
+        call(C.byref(job), _ptr(lab), g1 - g0, int(max_item_cells), C.byref(part))
+    return out
+
+
+def group_moments_rows(counts: np.ndarray, depth: np.ndarray, group, n_groups: int, cells=None,
+                       max_item_cells: int = 0, device: int = 0) -> dict:
+    """mgp_rows_group_moments: Engine.group_moments on caller-supplied u32 rows (counts [n, L, 8], depth
+    [n, L]), no engine context."""
+    lib = load_library()
+    counts = np.ascontiguousarray(counts, np.uint32)
+    depth = np.ascontiguousarray(depth, np.uint32)
+    n_rows, L = depth.shape
+    if counts.shape != (n_rows, L, 8):
+        raise InvalidInputError("counts must be [n, L, 8]")
+
+    def call(*args):
+        _ck(lib.mgp_rows_group_moments(int(device), _ptr(counts), _ptr(depth), int(n_rows), int(L), *args),
+            "mgp_rows_group_moments")
+
+    return _group_calls(call, n_rows, L, group, n_groups, cells, max_item_cells)
 
 
 def _coverage_calls(call, n_rows: int, L: int):
@@ -1336,6 +1401,19 @@ class Engine:
         allele frequencies of the cells with depth >= low_coverage_threshold (0: all).
         At most VARIANT_MAX_CELLS cells per call, every count below 2^24."""
         return self._variant_calls()[0](cells, low_coverage_threshold)
+
+    def group_moments(self, group, n_groups: int, cells=None, max_item_cells: int = 0) -> dict:
+        """mgp_group_moments_run (after run(), or on a ready table): the pseudobulk of every group of the
+        population `cells` (as for variant_moments) in one sweep. group[k] is entry k's label, 0 .. n_groups - 1
+        or -1 (in no group). A dict of GROUP_FIELDS arrays: per group, position and base the exact sums of the
+        fwd and of the rev counts ([n_groups, L, 4] uint64), the depth sum `cov` ([n_groups, L]), and the
+        cells with fwd + rev > 0 (`n_det`) and with fwd >= 2 and rev >= 2 (`n_conf`, uint32). The same bytes
+        for every max_item_cells (0: sized to fill the device). At most VARIANT_MAX_CELLS cells per call,
+        every count below 2^24; more than GROUP_MAX_GROUPS groups go in several device calls."""
+        def call(*args):
+            _ck(self.lib.mgp_group_moments_run(self._h, *args), "mgp_group_moments_run")
+
+        return _group_calls(call, self.cfg.n_cells, self.cfg.mito_len, group, n_groups, cells, max_item_cells)
 
     def variant_dev2(self, mean_af, cells=None, low_coverage_threshold: int = 0) -> np.ndarray:
         """mgp_variant_dev2_run (pass 2): [L, 4] sums of (af - mean_af)^2 over the cells of

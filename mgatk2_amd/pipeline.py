@@ -81,7 +81,7 @@ def analysis_settings(call_variants=False, variant_min_cells=5, variant_min_stra
                       variant_stabilize=False, variant_low_coverage=10, variant_min_coverage=1, coverage_stats=False,
                       cell_min_mean_coverage=0.0, cell_min_coverage_breadth=0.0, recompute_reference=False,
                       cluster=False, clones=None, neighbors=None, snn_prune=1.0 / 15.0, clonotypes=False,
-                      clonotype_resolution=1.0) -> dict:
+                      clonotype_resolution=1.0, groups=None, group_min_cells=2, group_min_af=0.01) -> dict:
     """The analysis keywords of run_pipeline / analyze_outputs checked (options.REQUIRES and each
     analysis's own range, InvalidInputError) and in the form enable_analyses and the writers take."""
     s: dict[str, Any] = {}
@@ -107,11 +107,20 @@ def analysis_settings(call_variants=False, variant_min_cells=5, variant_min_stra
     s["neighbors"] = None if neighbors is None else check_neighbors(neighbors)
     s["snn_prune"] = check_prune(snn_prune)
     s["clonotype_resolution"] = check_resolution(clonotype_resolution)
+    # pseudobulk counts and marker variants per cell group (off unless asked for): groups/ in the output;
+    # `groups` is a groups file or a {barcode: group} mapping, resolved over the run's cells before the run
+    s["groups"] = groups
+    if groups is not None:
+        from .analysis.groups import check_group_min_af, check_group_min_cells
+
+        group_min_cells, group_min_af = check_group_min_cells(group_min_cells), check_group_min_af(group_min_af)
+    s["group_min_cells"], s["group_min_af"] = group_min_cells, group_min_af
     return s
 
 
-def enable_analyses(processor, s) -> None:
-    """Turn on, on a CellProcessor, the analyses that `s` (an object with analysis_settings' names) asks for."""
+def enable_analyses(processor, s, names=None) -> None:
+    """Turn on, on a CellProcessor, the analyses that `s` (an object with analysis_settings' names) asks for.
+    names: the barcode of each cell of the run (of each column of a loaded table), for the groups."""
     if s.call_variants:
         processor.enable_variants(**s.variant_options)
     if s.coverage_on:
@@ -122,6 +131,10 @@ def enable_analyses(processor, s) -> None:
         processor.enable_neighbors(s.neighbors, s.snn_prune)
     if s.clonotypes:
         processor.enable_clonotypes(s.clonotype_resolution)
+    if getattr(s, "groups", None) is not None:
+        from .analysis.groups import resolve_groups
+
+        processor.enable_groups(*resolve_groups(s.groups, list(names or [])), s.group_min_cells, s.group_min_af)
 
 
 def write_table_outputs(processor, res, names: list[str], output_dir, output_format: str, coverage_on: bool,
@@ -142,6 +155,16 @@ def write_table_outputs(processor, res, names: list[str], output_dir, output_for
         write_variant_outputs(res.variants, res.allele_freq, af_names, output_dir, output_format)
         logger.info("%d variants called", len(res.variants))
     return af_names
+
+
+def write_group_outputs(res, output_dir) -> None:
+    """groups/ of a result whose run had the groups on (analysis/groups.py)."""
+    if res.groups is None:
+        return
+    from .analysis.groups import write_group_result
+
+    write_group_result(res.groups, output_dir)
+    logger.info("%d groups, %d marker variants", len(res.groups.group_names), len(res.groups.markers))
 
 
 def write_stage_outputs(processor, res, af_names: list[str], output_dir) -> None:
@@ -194,6 +217,9 @@ class MtDNAPipeline:
         snn_prune: float = 1.0 / 15.0,
         clonotypes: bool = False,
         clonotype_resolution: float = 1.0,
+        groups=None,
+        group_min_cells: int = 2,
+        group_min_af: float = 0.01,
     ):
         self.bam_path = Path(bam_path)
         # streamed ingest (default; MGP_STREAM=0 decodes the whole chrM set first)
@@ -214,7 +240,7 @@ class MtDNAPipeline:
             call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
             variant_low_coverage, variant_min_coverage, coverage_stats, cell_min_mean_coverage,
             cell_min_coverage_breadth, recompute_reference, cluster, clones, neighbors, snn_prune, clonotypes,
-            clonotype_resolution))
+            clonotype_resolution, groups, group_min_cells, group_min_af))
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -262,7 +288,7 @@ class MtDNAPipeline:
         else:
             # the HDF5 chunks are deflated on the device at the end of the run (mgp_h5_tiles)
             processor.enable_device_h5(self.barcode_list)
-        enable_analyses(processor, self)
+        enable_analyses(processor, self, self.barcode_list)
         if self.stream:
             # one pass: batches decoded on a producer thread, each pushed to the device as
             # it is ready, the windows piled as their reads arrive (readers.py:84-93)
@@ -318,6 +344,7 @@ class MtDNAPipeline:
         write_run_summary(meta, qc_dir / "summary.txt")
         af_names = write_table_outputs(processor, res, self.barcode_list, self.output_dir, self.output_format,
                                        self.coverage_on, self.coverage_stats, self.call_variants)
+        write_group_outputs(res, self.output_dir)
         t3 = time.time()
         gc.collect()
 
@@ -400,6 +427,9 @@ def run_pipeline(
     clonotypes: bool = False,
     clonotype_resolution: float = 1.0,
     device_inflate: bool = False,
+    groups=None,
+    group_min_cells: int = 2,
+    group_min_af: float = 0.01,
 ) -> dict[str, Any]:
     """pipeline.py:183-269. ``min_distance_from_end`` is accepted and, as in the
     reference, not passed on (the engine uses 5). ``call_variants``
@@ -419,7 +449,10 @@ def run_pipeline(
     SNN graph on the device, the same on every run (``clonotype_resolution`` as Seurat's resolution),
     and writes variants/cell_clonotypes.tsv and clonotypes.tsv. ``device_inflate`` inflates the BAM's
     BGZF blocks on the device (the first of ``devices``) instead of the host pool; the outputs are the
-    same bytes."""
+    same bytes. ``groups`` (a groups file: barcode, group; or a {barcode: group} mapping) writes groups/: the
+    pseudobulk counts of every group at all positions and bases and its marker variants, those with at least
+    ``group_min_cells`` confident cells and a pseudobulk heteroplasmy of at least ``group_min_af`` that
+    exceeds the rest of the population's (this project's thresholds; mgatk defines none)."""
     barcode_metadata = None
     if barcode_file is None:
         from .file_io.barcode_extraction import extract_barcodes_from_bam
@@ -462,6 +495,7 @@ def run_pipeline(
         cell_min_mean_coverage=cell_min_mean_coverage, cell_min_coverage_breadth=cell_min_coverage_breadth,
         recompute_reference=recompute_reference, cluster=cluster, clones=clones,
         neighbors=neighbors, snn_prune=snn_prune, clonotypes=clonotypes, clonotype_resolution=clonotype_resolution,
+        groups=groups, group_min_cells=group_min_cells, group_min_af=group_min_af,
     )
     return pipeline.run()
 
@@ -494,7 +528,8 @@ def analyze_outputs(input_dir, output_dir=None, barcodes=None, device: int = 0, 
     list; the population is those columns in file order), then the rest, on the device. Every
     column of the files is a cell, the reference alleles are the files', and the values are
     the stored min(count, 65535): the results equal R's on the files exactly, and a run's own
-    wherever no count saturates. Writes coverage/ and variants/ into ``output_dir`` (default:
+    wherever no count saturates. ``groups`` (with ``group_min_cells``, ``group_min_af``) labels the
+    files' columns. Writes coverage/, variants/ and groups/ into ``output_dir`` (default:
     ``input_dir``); the count files are never rewritten. ``host_inflate``: libhdf5 inflates
     the chunks instead of the device (the same results)."""
     from .engine import EngineResult
@@ -511,7 +546,7 @@ def analyze_outputs(input_dir, output_dir=None, barcodes=None, device: int = 0, 
             pop, names = _subset_columns(loaded.barcodes, barcodes)
         processor = CellProcessor(PipelineConfig(), out_dir, device=device)
         processor.reference, processor.population = loaded.ref_alleles, pop
-        enable_analyses(processor, s)
+        enable_analyses(processor, s, loaded.barcodes)
         # the minimal result of a run: every column of the files is a cell that passed
         res = EngineResult.alloc(n, L, dense=False)
         res.passed[:] = 1
@@ -520,6 +555,7 @@ def analyze_outputs(input_dir, output_dir=None, barcodes=None, device: int = 0, 
     out_dir.mkdir(parents=True, exist_ok=True)
     af_names = write_table_outputs(processor, res, names, out_dir, "hdf5", s.coverage_on, s.coverage_stats,
                                    s.call_variants)
+    write_group_outputs(res, out_dir)
     write_stage_outputs(processor, res, af_names, out_dir)
     t3 = time.time()
     timings = {"load": t1 - t0, **{"load_" + k: v for k, v in loaded.seconds.items()}, "analyses": t2 - t1,

@@ -158,6 +158,7 @@ class CellProcessor:
         self.h5_out = None
         self.variants_opt: dict | None = None
         self.coverage_opt: dict | None = None
+        self.groups_opt: dict | None = None
         self.stage_opt: dict[str, dict] = {}  # the analyses turned on (enable), by stage key
         # what a loaded table sets (analyze_outputs): the file's reference alleles in place of the
         # tally's, and the population in place of every cell (a subset of the file's columns)
@@ -287,6 +288,40 @@ class CellProcessor:
 
         res.coverage = run_coverage(parts, cells=self._analysis_population(res), **self.coverage_opt)
 
+    def enable_groups(self, labels, group_names: list[str], min_cells: int = 2, min_af: float = 0.01):
+        """Pseudobulk counts and marker variants per cell group from the devices' rows before their contexts
+        close (mgp_group_moments; analysis/groups.py): the run's result then carries `groups`, a GroupResult.
+        labels[c]: the group number of the run's cell c (of a loaded table's column c), 0 .. len(group_names)
+        - 1, or -1 for a cell in no group. The population is the variants': every cell of the run (one that
+        did not pass is an all-zero row and counts in its group's n_cells only), or the coverage filter's
+        kept cells, with the recomputed reference when there is one. The thresholds of the marker variants
+        are this project's choice; mgatk defines none."""
+        from ..analysis.groups import check_group_min_af, check_group_min_cells
+
+        labels = np.ascontiguousarray(labels, np.int32)
+        if not group_names or (labels.size and (labels.min() < -1 or labels.max() >= len(group_names))):
+            raise InvalidInputError("enable_groups: a label is outside the group names")
+        self.groups_opt = dict(labels=labels, group_names=list(group_names), min_cells=check_group_min_cells(min_cells),
+                               min_af=check_group_min_af(min_af))
+
+    def _call_groups(self, res: EngineResult, parts: DeviceParts) -> None:
+        from ..analysis.groups import group_result
+
+        opt = self.groups_opt
+        pop, ref = self._analysis_population(res), self.run_reference(res)
+        # the cell (or column) each entry of the population is, whether it has rows or not
+        ids = np.arange(pop.size, dtype=np.int64) if self.population is None else np.asarray(self.population, np.int64)
+        cov = res.coverage
+        if self.coverage_opt is not None and cov is not None:  # (as _call_variants)
+            pop, ids = cov.kept_cells, ids[cov.kept]
+            if cov.ref_alleles is not None:
+                ref = cov.ref_alleles
+        if ids.size and int(ids.max()) >= opt["labels"].size:
+            raise InvalidInputError(f"enable_groups: {opt['labels'].size} labels for a run of more cells")
+        labels = np.where(ids >= 0, opt["labels"][np.maximum(ids, 0)], -1)
+        res.groups = group_result(parts, labels, opt["group_names"], ref, cells=pop, min_cells=opt["min_cells"],
+                                  min_af=opt["min_af"], variants=res.variants)
+
     def _h5_device_on(self) -> bool:
         return self.h5_out is not None and os.environ.get("MGP_H5_DEVICE", "1") != "0"
 
@@ -304,12 +339,13 @@ class CellProcessor:
     def _after_run(self, res: EngineResult, parts: list, writers: bool = True) -> dict:
         """What is made of the devices' rows while their contexts are open, over parts =
         [(engine, lo, hi)] (shard.DeviceParts): the device txt writer, the device HDF5 writer,
-        the coverage pass, then the variants (which use its kept cells), each when enabled.
-        Returns the seconds of each under its last_timing key: txt_device and h5_device
-        always (writers=False: neither is run nor reported), coverage and variants when
-        enabled. A run without cells has no parts and makes nothing."""
+        the coverage pass, then the variants (which use its kept cells), then the groups (which
+        use both), each when enabled. Returns the seconds of each under its last_timing key:
+        txt_device and h5_device always (writers=False: neither is run nor reported), coverage,
+        variants and groups when enabled. A run without cells has no parts and makes nothing."""
         steps = [("coverage", self.coverage_opt is not None, self._call_coverage),
-                 ("variants", self.variants_opt is not None, self._call_variants)]
+                 ("variants", self.variants_opt is not None, self._call_variants),
+                 ("groups", self.groups_opt is not None, self._call_groups)]
         seconds = {}
         if writers:
             steps = [("txt_device", self._txt_device_on(), self._write_txt),
