@@ -74,7 +74,10 @@ extern "C" {
                                  the cells' clonotypes),
                                  mgp_bgzf_inflate, mgp_inflater_* (BGZF inflate on the device),
                                  mgp_group_moments_run, mgp_rows_group_moments (pseudobulk counts
-                                 per cell group on the device) */
+                                 per cell group on the device),
+                                 mgp_rank_sums (the rank sums of every feature per group on the
+                                 device: the rank-sum test of each variant, a group against the
+                                 rest) */
 
 /* ---- return codes (0 = success) ------------------------------------------ */
 #define MGP_OK               0
@@ -816,6 +819,30 @@ int  mgp_knn(int device, const double *x, int64_t n_items, int64_t n_feat, int32
 int  mgp_snn(int device, const int32_t *knn_idx /* [n][k] */, int64_t n_items, int32_t k, int32_t min_shared,
              int64_t capacity, int64_t *n_edges, int32_t *out_i, int32_t *out_j,
              int32_t *out_shared /* [capacity] each, may be NULL when capacity == 0 */);
+/* The rank sums of every feature per group on the device (added under ABI 7): the integers of the
+ * Wilcoxon rank-sum test of each variant, a group against the rest (Seurat's FindAllMarkers on the
+ * alleles assay, the question after FindClonotypes). No engine context, buffers of the call's
+ * own, all freed on return. Items are the columns of x [n_feat][n_items] as for mgp_pair_dist
+ * (the heteroplasmy matrix: each variant's cells contiguous); group[i] in 0 .. n_groups - 1 labels
+ * item i. Per feature f the items are ordered by value, -0.0 equal to +0.0; a tie class is a
+ * maximal run of equal values at the 0-based sorted positions lo..hi and each member has the
+ * midrank (lo + hi + 2) / 2.
+ *   out_r2[f][g]  = the sum over the items of group g of lo + hi + 2  (<= 2 n^2 <= 2^41)
+ *   out_pos[f][g] = the items of group g with a value > 0
+ *   out_ties[f]   = the sum over the tie classes of t^3 - t, t = hi - lo + 1  (<= 2^60)
+ * Integer sums: exact, and a function of the input alone (the sort is one sort per feature for
+ * every group; neither it, nor MGP_RANK_TILE, the elements sorted in LDS at a time, a power of
+ * two from 64 to 4096, nor MGP_RANK_BATCH, the features of a batch, 0 or unset: automatic,
+ * changes a result).
+ * Bounds, checked before any allocation or device call (MGP_E_INVALID): no null pointer, no
+ * negative count, n_items <= 2^20, n_feat <= 2^24, 1 <= n_groups <= 65536. Checked on the device
+ * before anything is trusted (MGP_E_INVALID): every label in range, every value finite.
+ * n_items == 0 or n_feat == 0: nothing is launched, the outputs are zeroed.
+ * Device memory: 4 n, and per feature of a batch 8 n + 12 P + 12 n_groups + 8 bytes, P the next
+ * power of two >= n; a batch is what 1 GiB holds. */
+int  mgp_rank_sums(int device, const double *x /* [n_feat][n_items] */, int64_t n_items, int64_t n_feat,
+                   const int32_t *group /* [n_items] */, int32_t n_groups, uint64_t *out_r2 /* [n_feat][n_groups] */,
+                   uint32_t *out_pos /* [n_feat][n_groups] */, uint64_t *out_ties /* [n_feat] */);
 /* Louvain communities of an integer-weighted graph on the device (added under ABI 7): the second
  * half of Signac's FindClonotypes, FindClusters on the SNN graph, which gives each cell its
  * clonotype. The CPU tools visit the vertices one by one in a random order; here a pass is

@@ -261,6 +261,7 @@ class GroupResult:
     allele_freq: np.ndarray | None = None  # [n called variants, n_groups], with the run's variant table
     variant_names: list[str] | None = None
     seconds: dict = field(default_factory=dict)
+    tests: object | None = None  # with the rank-sum tests on: the GroupTestTable (analysis/group_tests.py)
 
 
 def group_result(source, labels, group_names: list[str], ref_alleles: list[str], cells=None, min_cells: int = 2,
@@ -354,8 +355,8 @@ def groups_dir(output_dir) -> Path:
 
 
 def write_group_result(res: GroupResult, output_dir) -> Path:
-    """The run's groups/ directory: groups.tsv, group_counts.h5, group_variants.tsv and, when the run called
-    variants and its table is not empty, group_allele_freq.tsv."""
+    """The run's groups/ directory: groups.tsv, group_counts.h5, group_variants.tsv, when the run called
+    variants and its table is not empty, group_allele_freq.tsv, and with the rank-sum tests on, group_tests.tsv."""
     gdir = groups_dir(output_dir)
     write_group_table(res.table, gdir / "groups.tsv")
     write_group_counts_h5(res.moments, res.group_names, res.table.n_cells[:-1], res.ref_alleles,
@@ -363,4 +364,8 @@ def write_group_result(res: GroupResult, output_dir) -> Path:
     write_marker_table(res.markers, res.group_names, gdir / "group_variants.tsv")
     if res.allele_freq is not None:
         write_group_allele_freq(res.allele_freq, res.variant_names, res.group_names, gdir / "group_allele_freq.tsv")
+    if res.tests is not None:
+        from .group_tests import write_group_tests
+
+        write_group_tests(res.tests, res.group_names, gdir / "group_tests.tsv")
     return gdir

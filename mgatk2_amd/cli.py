@@ -11,7 +11,9 @@ the device, the trees and heatmap orders in variants/), and ``--neighbors K`` / 
 (the cells' kNN and SNN graphs by heteroplasmy on the device, in variants/), and ``--clonotypes`` /
 ``--clonotype-resolution R`` (the Louvain communities of that SNN graph on the device: each cell's
 clonotype, in variants/), and ``--groups FILE`` / ``--group-min-cells N`` / ``--group-min-af F`` (the
-pseudobulk counts and marker variants of every cell group of FILE from the device's rows, groups/).
+pseudobulk counts and marker variants of every cell group of FILE from the device's rows, groups/), and
+``--group-test`` / ``--group-test-max-p P`` (the rank-sum test of each variant, every group against the rest
+of the cells, ranked on the device: groups/group_tests.tsv).
 Not carried over: ``hardmask-fasta`` (FASTA masking utility, outside the hot path).
 """
 
@@ -97,6 +99,13 @@ def _group_option_list() -> list:
         click.option("--group-min-af", default=None, type=click.FloatRange(min=0.0, max=1.0), metavar="F",
                      help="Pseudobulk heteroplasmy in the group a marker variant needs  [default: 0.01]; "
                           "needs --groups"),
+        click.option("--group-test", "group_test", is_flag=True,
+                     help="Wilcoxon rank-sum test of each marker or called variant's heteroplasmy, every group "
+                          "against the rest of the cells, ranked on the device (groups/group_tests.tsv, as Seurat's "
+                          "FindAllMarkers); needs --groups"),
+        click.option("--group-test-max-p", default=None, type=click.FloatRange(min=0.0, max=1.0), metavar="P",
+                     help="Largest p-value of a written line (Seurat's return.thresh)  [default: 0.01]; needs "
+                          "--group-test"),
     ]
 
 
@@ -123,12 +132,13 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
                   variant_low_coverage, variant_min_coverage, coverage_stats=False, cell_min_mean_coverage=0.0,
                   cell_min_coverage_breadth=0.0, recompute_reference=False, cluster=False, clones=None, neighbors=None,
                   snn_prune=None, clonotypes=False, clonotype_resolution=None, device_inflate=False, groups=None,
-                  group_min_cells=None, group_min_af=None) -> dict:
+                  group_min_cells=None, group_min_af=None, group_test=False, group_test_max_p=None) -> dict:
     """The options run_pipeline gets beyond the reference's, each only when asked for: the variant
     options with --variants; the four coverage options with --coverage-stats, otherwise the filter
     thresholds and --recompute-reference that were given; the analysis options that were given (one
     that lacks what it needs, options.REQUIRES, or is out of range: a usage error); --device-inflate; --groups
-    and the thresholds given with it (one given without --groups: a usage error)."""
+    and the thresholds given with it (one given without --groups: a usage error); --group-test (without --groups:
+    a usage error) and --group-test-max-p when given (without --group-test: a usage error)."""
     from .options import AnalysisOptions
 
     opts = AnalysisOptions(call_variants, cluster, clones, neighbors, snn_prune, clonotypes, clonotype_resolution)
@@ -158,6 +168,14 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
     for flag, value in (("--group-min-cells", group_min_cells), ("--group-min-af", group_min_af)):
         if value is not None and groups is None:
             raise click.UsageError(f"{flag} requires --groups")
+    if group_test and groups is None:
+        raise click.UsageError("--group-test requires --groups")
+    if group_test_max_p is not None and not group_test:
+        raise click.UsageError("--group-test-max-p requires --group-test")
+    if group_test:
+        out.update(group_test=True)
+        if group_test_max_p is not None:
+            out.update(group_test_max_p=group_test_max_p)
     if groups is not None:
         out.update(groups=str(groups))
         out.update({k: v for k, v in (("group_min_cells", group_min_cells), ("group_min_af", group_min_af))
@@ -381,6 +399,8 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
         if variant_args and variant_args.get("groups") is not None:
             logger.info("  Cell groups:            %s, min cells %s, min heteroplasmy %s", variant_args["groups"],
                         variant_args.get("group_min_cells", 2), variant_args.get("group_min_af", 0.01))
+        if variant_args and variant_args.get("group_test"):
+            logger.info("  Group rank-sum tests:   max p %s", variant_args.get("group_test_max_p", 0.01))
         if variant_args and variant_args.get("device_inflate"):
             logger.info("  BGZF inflate:           on the device")
         if dry_run:

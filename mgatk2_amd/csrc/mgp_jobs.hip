@@ -24,6 +24,7 @@
 #include "mgp_jobs.h"
 #include "mgp_louvain.h"
 #include "mgp_qc.h"
+#include "mgp_rank.h"
 #include "mgp_txtgz.h"
 #include "mgp_variants.h"
 
@@ -72,6 +73,11 @@ struct ClusterState {
 struct GraphState {
     DevBuf x, bad, part_dist, part_idx, out_dist, out_idx;                 // mgp_knn
     DevBuf idx, sets, deg, off, cur, rev, cnt, eoff, ei, ej, es;  // mgp_snn
+};
+
+// mgp_rank_sums: the rank sums' buffers (mgp_rank.hip), a call's own
+struct RankState {
+    DevBuf x, group, keys, pay, r2, pos, ties, bad;
 };
 
 // mgp_louvain: the community detection's buffers (mgp_louvain.hip), a call's own
@@ -506,6 +512,11 @@ struct VarProf {
         float ms = 0;
         if (a && b && hipEventElapsedTime(&ms, a, b) == hipSuccess)
             std::fprintf(stderr, "[%s] %lld x %lld %s: kernels %.3f ms\n", who, (long long)n, (long long)m, what, ms);
+    }
+    // (after the stream is synchronised) the milliseconds alone, 0 when not measured
+    float ms() {
+        float v = 0;
+        return a && b && hipEventElapsedTime(&v, a, b) == hipSuccess ? v : 0.0f;
     }
     ~VarProf() {
         if (a) (void)hipEventDestroy(a);
@@ -1280,6 +1291,91 @@ int mgp_snn(int device, const int32_t* knn_idx, int64_t n_items, int32_t k, int3
     });
 }
 
+// an integer threshold from the environment, read at call time: unset or not in lo..hi gives dflt
+static int lv_env(const char* name, int lo, int hi, int dflt) {
+    const char* e = std::getenv(name);
+    if (!e || !*e) return dflt;
+    const long v = std::strtol(e, nullptr, 10);
+    return v < lo || v > hi ? dflt : (int)v;
+}
+
+// ---------------------------------------------------------------------------
+// mgp_rank_sums: per feature (a row of x) the items sorted once, then every group's doubled
+// midrank sum, its count of values > 0 and the row's tie term (mgp_rank.h): the integers of the
+// Wilcoxon rank-sum test of each variant, a group against the rest (Seurat's FindAllMarkers on
+// the alleles assay). No engine context, as the graphs. The features go in batches that keep
+// the call's device memory under rank::kBudget; the results do not depend on the batch.
+// ---------------------------------------------------------------------------
+int mgp_rank_sums(int device, const double* x, int64_t n_items, int64_t n_feat, const int32_t* group, int32_t n_groups,
+                  uint64_t* out_r2, uint32_t* out_pos, uint64_t* out_ties) {
+    const char* who = "mgp_rank_sums";
+    if (n_items < 0 || n_feat < 0) return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    if (n_items > rank::kMaxItems) return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^20 items in one call");
+    if (n_feat > rank::kMaxFeat) return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^24 features in one call");
+    if (n_groups < 1 || n_groups > rank::kMaxGroups)
+        return set_err(MGP_E_INVALID, std::string(who) + ": n_groups must be in 1..65536");
+    if ((n_feat > 0 && (!out_r2 || !out_pos || !out_ties)) || (n_items > 0 && !group) ||
+        (n_items > 0 && n_feat > 0 && !x))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    const size_t nf = (size_t)n_feat, ng = (size_t)n_groups;
+    if (n_items == 0 || n_feat == 0) {  // nothing is ranked: every sum is 0
+        if (nf) {
+            std::fill(out_r2, out_r2 + nf * ng, (uint64_t)0);
+            std::fill(out_pos, out_pos + nf * ng, (uint32_t)0);
+            std::fill(out_ties, out_ties + nf, (uint64_t)0);
+        }
+        return MGP_OK;
+    }
+    const int tile = rank::tile_of(lv_env("MGP_RANK_TILE", rank::kMinTile, rank::kMaxTile, rank::kMaxTile));
+    const int64_t batch = rank::batch_features(n_items, n_feat, n_groups, lv_env("MGP_RANK_BATCH", 0, 1 << 24, 0));
+    return cl_call<RankState>(device, [&](RankState& st, hipStream_t s) {
+        const size_t n = (size_t)n_items, P = (size_t)rank::padded(n_items), rows = (size_t)batch;
+        MGP_TRY(st.group.ensure(n * 4));
+        MGP_TRY(st.bad.ensure(4));
+        MGP_TRY(st.x.ensure(rows * n * 8));
+        MGP_TRY(st.keys.ensure(rows * P * 8));
+        MGP_TRY(st.pay.ensure(rows * P * 4));
+        MGP_TRY(st.r2.ensure(rows * ng * 8));
+        MGP_TRY(st.pos.ensure(rows * ng * 4));
+        MGP_TRY(st.ties.ensure(rows * 8));
+        uint32_t bad = 0;
+        auto fetch_bad = [&]() -> int {
+            HIP_TRY(hipMemcpyAsync(&bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            return MGP_OK;
+        };
+        // the labels first: no kernel indexes by one before they are known to be in range
+        HIP_TRY(hipMemcpyAsync(st.group.p, group, n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(st.bad.p, 0, 4, s));
+        if (rank::check_labels(st.group.as<int32_t>(), (int)n_items, n_groups, st.bad.as<uint32_t>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+        MGP_TRY(fetch_bad());
+        if (bad) return set_err(MGP_E_INVALID, std::string(who) + ": a group label is outside 0 .. n_groups - 1");
+        float kernel_ms = 0;
+        for (size_t f0 = 0; f0 < nf; f0 += rows) {
+            const size_t b = std::min(rows, nf - f0);
+            HIP_TRY(hipMemcpyAsync(st.x.p, x + f0 * n, b * n * 8, hipMemcpyHostToDevice, s));
+            VarProf prof(s);
+            if (rank::sums(st.x.as<double>(), st.group.as<int32_t>(), (int)n_items, (int64_t)b, n_groups, tile,
+                           st.keys.as<uint64_t>(), st.pay.as<uint32_t>(), st.r2.as<uint64_t>(), st.pos.as<uint32_t>(),
+                           st.ties.as<uint64_t>(), st.bad.as<uint32_t>(), s) != 0)
+                return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+            prof.stop();
+            MGP_TRY(fetch_bad());
+            kernel_ms += prof.ms();
+            if (bad) return set_err(MGP_E_INVALID, std::string(who) + ": a value of x is not finite");
+            HIP_TRY(hipMemcpyAsync(out_r2 + f0 * ng, st.r2.p, b * ng * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(out_pos + f0 * ng, st.pos.p, b * ng * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(out_ties + f0, st.ties.p, b * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        if (std::getenv("MGP_VAR_PROF"))
+            std::fprintf(stderr, "[%s] %lld x %lld items x features, %d groups, tile %d, batch %lld: kernels %.3f ms\n", who,
+                         (long long)n_items, (long long)n_feat, (int)n_groups, tile, (long long)batch, kernel_ms);
+        return (int)MGP_OK;
+    });
+}
+
 // ---------------------------------------------------------------------------
 // mgp_louvain: the communities of an integer-weighted graph, the cells' clonotypes when the graph
 // is mgp_snn's (Signac's FindClonotypes -> FindClusters). The definition is pinned in
@@ -1293,14 +1389,6 @@ static double lv_score(uint64_t m2, uint64_t internal, unsigned __int128 b, doub
     const double x = (double)m2 * (double)internal;
     const double y = gamma * (double)b;
     return x - y;
-}
-
-// an integer threshold from the environment, read at call time: unset or not in lo..hi gives dflt
-static int lv_env(const char* name, int lo, int hi, int dflt) {
-    const char* e = std::getenv(name);
-    if (!e || !*e) return dflt;
-    const long v = std::strtol(e, nullptr, 10);
-    return v < lo || v > hi ? dflt : (int)v;
 }
 
 int mgp_louvain(int device, int64_t n_vertices, int64_t n_edges, const int32_t* edge_i, const int32_t* edge_j,

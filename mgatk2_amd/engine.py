@@ -48,7 +48,7 @@ ABI_SYMBOLS = (
     "mgp_knn", "mgp_snn", "mgp_louvain", "mgp_bgzf_inflate", "mgp_inflater_create", "mgp_inflater_destroy",
     "mgp_inflater_run", "mgp_inflater_host_alloc", "mgp_inflater_host_release", "mgp_inflater_times",
     "mgp_zlib_inflate", "mgp_open_table", "mgp_table_load", "mgp_table_load_planes", "mgp_table_check",
-    "mgp_table_ready", "mgp_group_moments_run", "mgp_rows_group_moments",
+    "mgp_table_ready", "mgp_group_moments_run", "mgp_rows_group_moments", "mgp_rank_sums",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -357,6 +357,7 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_hclust_dist": ([C.c_int, vp, i64, vp, vp, vp], C.c_int),
         "mgp_hclust": ([C.c_int, vp, i64, i64, vp, vp, vp, vp], C.c_int),
         "mgp_knn": ([C.c_int, vp, i64, i64, i32, vp, vp], C.c_int),
+        "mgp_rank_sums": ([C.c_int, vp, i64, i64, vp, i32, vp, vp, vp], C.c_int),
         "mgp_snn": ([C.c_int, vp, i64, i32, i32, i64, C.POINTER(i64), vp, vp, vp], C.c_int),
         "mgp_louvain": (
             [C.c_int, i64, i64, vp, vp, vp, C.c_double, i32, i32, vp, C.POINTER(i64), C.POINTER(C.c_double), vp,
@@ -969,6 +970,32 @@ def graph_snn(idx, min_shared: int, device: int = 0):
         order = np.lexsort((out[1], out[0]))
         out = [a[order] for a in out]
     return tuple(out)
+
+
+RANK_MAX_ITEMS = 1 << 20   # items of one mgp_rank_sums call
+RANK_MAX_GROUPS = 1 << 16  # groups of one call
+RANK_LDS_GROUPS = 2048     # groups up to here: the rank kernel's table is in LDS (rank::kLdsGroups)
+
+
+def rank_sums(x, group, n_groups: int, device: int = 0) -> dict:
+    """mgp_rank_sums: per feature (row of x [n_feat, n_items], fp64, every value finite) the items ordered by
+    value (-0.0 equals +0.0), a tie class at the 0-based sorted positions lo..hi having the midrank
+    (lo + hi + 2) / 2. group[i] in 0 .. n_groups - 1 labels item i (checked on the device). A dict: `r2`
+    [n_feat, n_groups] uint64, the sum over the group's items of lo + hi + 2; `pos` [n_feat, n_groups] uint32,
+    the group's items with a value > 0; `ties` [n_feat] uint64, the sum over the tie classes of t^3 - t. Exact
+    integers, a function of the input alone. At most RANK_MAX_ITEMS items and RANK_MAX_GROUPS groups."""
+    x = _cluster_x(x)
+    nf, n = x.shape
+    group = np.ascontiguousarray(group, np.int32)
+    if group.shape != (n,):
+        raise InvalidInputError(f"rank_sums: {group.shape[0] if group.ndim == 1 else group.shape} labels for {n} items")
+    n_groups = int(n_groups)
+    ok = n <= RANK_MAX_ITEMS and 1 <= n_groups <= RANK_MAX_GROUPS  # (otherwise refused before any use)
+    shape = (nf, n_groups) if ok else (0, 0)
+    out = {"r2": np.zeros(shape, np.uint64), "pos": np.zeros(shape, np.uint32), "ties": np.zeros(shape[0], np.uint64)}
+    _ck(load_library().mgp_rank_sums(int(device), _ptr(x), n, nf, _ptr(group), n_groups, _ptr(out["r2"]),
+                                     _ptr(out["pos"]), _ptr(out["ties"])), "mgp_rank_sums")
+    return out
 
 
 LOUVAIN_MAX_VERTICES = 1 << 20  # vertices of one mgp_louvain call

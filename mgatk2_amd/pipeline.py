@@ -81,7 +81,8 @@ def analysis_settings(call_variants=False, variant_min_cells=5, variant_min_stra
                       variant_stabilize=False, variant_low_coverage=10, variant_min_coverage=1, coverage_stats=False,
                       cell_min_mean_coverage=0.0, cell_min_coverage_breadth=0.0, recompute_reference=False,
                       cluster=False, clones=None, neighbors=None, snn_prune=1.0 / 15.0, clonotypes=False,
-                      clonotype_resolution=1.0, groups=None, group_min_cells=2, group_min_af=0.01) -> dict:
+                      clonotype_resolution=1.0, group_test=False, group_test_max_p=0.01, groups=None,
+                      group_min_cells=2, group_min_af=0.01) -> dict:
     """The analysis keywords of run_pipeline / analyze_outputs checked (options.REQUIRES and each
     analysis's own range, InvalidInputError) and in the form enable_analyses and the writers take."""
     s: dict[str, Any] = {}
@@ -115,6 +116,16 @@ def analysis_settings(call_variants=False, variant_min_cells=5, variant_min_stra
 
         group_min_cells, group_min_af = check_group_min_cells(group_min_cells), check_group_min_af(group_min_af)
     s["group_min_cells"], s["group_min_af"] = group_min_cells, group_min_af
+    # the rank-sum test of each tested variant, every group against the rest (off unless asked for):
+    # groups/group_tests.tsv
+    s["group_test"] = bool(group_test)
+    if s["group_test"]:
+        from .analysis.group_tests import check_group_test_max_p
+
+        if groups is None:
+            raise InvalidInputError("group_test requires groups")
+        group_test_max_p = check_group_test_max_p(group_test_max_p)
+    s["group_test_max_p"] = group_test_max_p
     return s
 
 
@@ -134,7 +145,8 @@ def enable_analyses(processor, s, names=None) -> None:
     if getattr(s, "groups", None) is not None:
         from .analysis.groups import resolve_groups
 
-        processor.enable_groups(*resolve_groups(s.groups, list(names or [])), s.group_min_cells, s.group_min_af)
+        processor.enable_groups(*resolve_groups(s.groups, list(names or [])), s.group_min_cells, s.group_min_af,
+                                getattr(s, "group_test", False), getattr(s, "group_test_max_p", 0.01))
 
 
 def write_table_outputs(processor, res, names: list[str], output_dir, output_format: str, coverage_on: bool,
@@ -165,6 +177,10 @@ def write_group_outputs(res, output_dir) -> None:
 
     write_group_result(res.groups, output_dir)
     logger.info("%d groups, %d marker variants", len(res.groups.group_names), len(res.groups.markers))
+    tests = res.groups.tests
+    if tests is not None:
+        logger.info("Rank-sum tests: %d variants tested over %d groups, %d lines with p <= %s", tests.n_tested,
+                    tests.n_groups, len(tests), tests.max_p)
 
 
 def write_stage_outputs(processor, res, af_names: list[str], output_dir) -> None:
@@ -220,6 +236,8 @@ class MtDNAPipeline:
         groups=None,
         group_min_cells: int = 2,
         group_min_af: float = 0.01,
+        group_test: bool = False,
+        group_test_max_p: float = 0.01,
     ):
         self.bam_path = Path(bam_path)
         # streamed ingest (default; MGP_STREAM=0 decodes the whole chrM set first)
@@ -240,7 +258,7 @@ class MtDNAPipeline:
             call_variants, variant_min_cells, variant_min_strand_cor, variant_min_vmr, variant_stabilize,
             variant_low_coverage, variant_min_coverage, coverage_stats, cell_min_mean_coverage,
             cell_min_coverage_breadth, recompute_reference, cluster, clones, neighbors, snn_prune, clonotypes,
-            clonotype_resolution, groups, group_min_cells, group_min_af))
+            clonotype_resolution, group_test, group_test_max_p, groups, group_min_cells, group_min_af))
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -430,6 +448,8 @@ def run_pipeline(
     groups=None,
     group_min_cells: int = 2,
     group_min_af: float = 0.01,
+    group_test: bool = False,
+    group_test_max_p: float = 0.01,
 ) -> dict[str, Any]:
     """pipeline.py:183-269. ``min_distance_from_end`` is accepted and, as in the
     reference, not passed on (the engine uses 5). ``call_variants``
@@ -452,7 +472,10 @@ def run_pipeline(
     same bytes. ``groups`` (a groups file: barcode, group; or a {barcode: group} mapping) writes groups/: the
     pseudobulk counts of every group at all positions and bases and its marker variants, those with at least
     ``group_min_cells`` confident cells and a pseudobulk heteroplasmy of at least ``group_min_af`` that
-    exceeds the rest of the population's (this project's thresholds; mgatk defines none)."""
+    exceeds the rest of the population's (this project's thresholds; mgatk defines none). ``group_test`` (needs
+    ``groups``) adds groups/group_tests.tsv: the Wilcoxon rank-sum test of each marker or called variant's
+    heteroplasmy over the cells, every group against the rest (Seurat's FindAllMarkers; the ranks on the device),
+    the pairs higher in the group with a p-value up to ``group_test_max_p``."""
     barcode_metadata = None
     if barcode_file is None:
         from .file_io.barcode_extraction import extract_barcodes_from_bam
@@ -495,7 +518,8 @@ def run_pipeline(
         cell_min_mean_coverage=cell_min_mean_coverage, cell_min_coverage_breadth=cell_min_coverage_breadth,
         recompute_reference=recompute_reference, cluster=cluster, clones=clones,
         neighbors=neighbors, snn_prune=snn_prune, clonotypes=clonotypes, clonotype_resolution=clonotype_resolution,
-        groups=groups, group_min_cells=group_min_cells, group_min_af=group_min_af,
+        groups=groups, group_min_cells=group_min_cells, group_min_af=group_min_af, group_test=group_test,
+        group_test_max_p=group_test_max_p,
     )
     return pipeline.run()
 
@@ -528,8 +552,8 @@ def analyze_outputs(input_dir, output_dir=None, barcodes=None, device: int = 0, 
     list; the population is those columns in file order), then the rest, on the device. Every
     column of the files is a cell, the reference alleles are the files', and the values are
     the stored min(count, 65535): the results equal R's on the files exactly, and a run's own
-    wherever no count saturates. ``groups`` (with ``group_min_cells``, ``group_min_af``) labels the
-    files' columns. Writes coverage/, variants/ and groups/ into ``output_dir`` (default:
+    wherever no count saturates. ``groups`` (with ``group_min_cells``, ``group_min_af``, ``group_test``,
+    ``group_test_max_p``) labels the files' columns. Writes coverage/, variants/ and groups/ into ``output_dir`` (default:
     ``input_dir``); the count files are never rewritten. ``host_inflate``: libhdf5 inflates
     the chunks instead of the device (the same results)."""
     from .engine import EngineResult

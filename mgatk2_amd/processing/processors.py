@@ -288,21 +288,26 @@ class CellProcessor:
 
         res.coverage = run_coverage(parts, cells=self._analysis_population(res), **self.coverage_opt)
 
-    def enable_groups(self, labels, group_names: list[str], min_cells: int = 2, min_af: float = 0.01):
+    def enable_groups(self, labels, group_names: list[str], min_cells: int = 2, min_af: float = 0.01,
+                      group_test: bool = False, group_test_max_p: float = 0.01):
         """Pseudobulk counts and marker variants per cell group from the devices' rows before their contexts
         close (mgp_group_moments; analysis/groups.py): the run's result then carries `groups`, a GroupResult.
         labels[c]: the group number of the run's cell c (of a loaded table's column c), 0 .. len(group_names)
         - 1, or -1 for a cell in no group. The population is the variants': every cell of the run (one that
         did not pass is an all-zero row and counts in its group's n_cells only), or the coverage filter's
         kept cells, with the recomputed reference when there is one. The thresholds of the marker variants
-        are this project's choice; mgatk defines none."""
+        are this project's choice; mgatk defines none. group_test: also the rank-sum test of each tested
+        variant, every group against the rest of the population (mgp_rank_sums; analysis/group_tests.py), the
+        pairs with a p-value up to group_test_max_p kept: the GroupResult's `tests`."""
+        from ..analysis.group_tests import check_group_test_max_p
         from ..analysis.groups import check_group_min_af, check_group_min_cells
 
         labels = np.ascontiguousarray(labels, np.int32)
         if not group_names or (labels.size and (labels.min() < -1 or labels.max() >= len(group_names))):
             raise InvalidInputError("enable_groups: a label is outside the group names")
         self.groups_opt = dict(labels=labels, group_names=list(group_names), min_cells=check_group_min_cells(min_cells),
-                               min_af=check_group_min_af(min_af))
+                               min_af=check_group_min_af(min_af), test=bool(group_test),
+                               test_max_p=check_group_test_max_p(group_test_max_p))
 
     def _call_groups(self, res: EngineResult, parts: DeviceParts) -> None:
         from ..analysis.groups import group_result
@@ -321,6 +326,17 @@ class CellProcessor:
         labels = np.where(ids >= 0, opt["labels"][np.maximum(ids, 0)], -1)
         res.groups = group_result(parts, labels, opt["group_names"], ref, cells=pop, min_cells=opt["min_cells"],
                                   min_af=opt["min_af"], variants=res.variants)
+        if opt["test"]:
+            # the marker variants and the run's called ones, ranked over the same population on the first device;
+            # their matrix by the route (and with the minimum coverage) of the variants' own
+            from ..analysis.group_tests import run_group_tests
+
+            t0 = time.perf_counter()
+            min_cov = 1 if self.variants_opt is None else self.variants_opt["min_coverage"]
+            res.groups.tests = run_group_tests(parts, res.groups.markers, labels, len(opt["group_names"]), ref,
+                                               cells=pop, variants=res.variants, min_coverage=min_cov,
+                                               max_p=opt["test_max_p"], device=self.devices[0])
+            res.groups.seconds["tests"] = time.perf_counter() - t0
 
     def _h5_device_on(self) -> bool:
         return self.h5_out is not None and os.environ.get("MGP_H5_DEVICE", "1") != "0"
