@@ -77,7 +77,9 @@ extern "C" {
                                  per cell group on the device),
                                  mgp_rank_sums (the rank sums of every feature per group on the
                                  device: the rank-sum test of each variant, a group against the
-                                 rest) */
+                                 rest),
+                                 mgp_pca, mgp_sym_eig (the principal components of the heteroplasmy
+                                 matrix and the symmetric eigensolver under them on the device) */
 
 /* ---- return codes (0 = success) ------------------------------------------ */
 #define MGP_OK               0
@@ -843,6 +845,59 @@ int  mgp_snn(int device, const int32_t *knn_idx /* [n][k] */, int64_t n_items, i
 int  mgp_rank_sums(int device, const double *x /* [n_feat][n_items] */, int64_t n_items, int64_t n_feat,
                    const int32_t *group /* [n_items] */, int32_t n_groups, uint64_t *out_r2 /* [n_feat][n_groups] */,
                    uint32_t *out_pos /* [n_feat][n_groups] */, uint64_t *out_ties /* [n_feat] */);
+/* Principal components of the heteroplasmy matrix on the device (added under ABI 7): the first use
+ * mgatk's vignette names for the matrix, dimensionality reduction; R's
+ * prcomp(t(af), center = TRUE, scale. = scale). No engine context, buffers of the call's own, all
+ * freed on return (MGP_E_OOM leaves nothing allocated). Items are the columns of
+ * x [n_feat = m][n_items = n] as for mgp_pair_dist, every value finite (MGP_E_INVALID from the
+ * device's check otherwise). Every result is a chain of single fp64 operations whose order the
+ * shape fixes, so the bytes are a function of the input alone: the same on every call, tiling and
+ * device (no float atomics, no reduction whose order depends on the grid).
+ * A slab is 1,024 consecutive items, the last may be short; the slab is part of the definition.
+ *   mean[f]   per slab s = s + x[f][i] in ascending i from 0.0; the slab sums added in ascending
+ *             slab order from 0.0; one division by n
+ *   xc        x - mean, one rounding
+ *   scale     var[f]: per slab s = fma(xc, xc, s), the slab sums added in order, / (n - 1);
+ *             sd = sqrt(var); z = xc / sd, and z = 0 with sd reported as 0 where sd == 0.
+ *             Without scale z = xc
+ *   cov[a][b] per slab s = fma(z[a][i], z[b][i], s) in ascending i from 0.0; the slab sums added in
+ *             order; one division by n - 1. Exactly symmetric (one triangle computed, mirrored)
+ *   eigen     mgp_sym_eig's result for cov (below)
+ *   scores    out_scores[c][i]: s = fma(z[f][i], out_loadings[c][f], s) in ascending f from 0.0
+ * Outputs: out_mean [m]; out_sd [m] (with scale the divisor; without, sqrt(cov[f][f]), and it may
+ * then be NULL); out_eig [m], all eigenvalues; out_loadings [n_comp][m], row c the eigenvector c;
+ * out_scores [n_comp][n]; out_cov [m][m] (may be NULL); *out_sweeps as mgp_sym_eig's.
+ * Bounds, checked before any allocation or device call (MGP_E_INVALID, each with its own message):
+ * no null pointer that is not optional, no negative count, 2 <= n_items <= 2^20, n_feat <= 2048,
+ * 1 <= n_comp <= min(n_feat, n_items - 1).
+ * MGP_PCA_TILE (16, 32 or 64; anything else or unset: by n_feat), the covariance kernel's tile edge,
+ * is read from the environment at call time and changes no result.
+ * Device memory, S = ceil(n / 1024): 16 n m (x and z) + 8 S m^2 (the covariance's slab partials:
+ * 32 GiB at both bounds) + 48 m^2 + 8 S m + 8 n_comp (m + n) bytes. */
+int  mgp_pca(int device, const double *x /* [n_feat][n_items] */, int64_t n_items, int64_t n_feat,
+             int32_t scale, int32_t n_comp, double *out_mean /* [m] */, double *out_sd /* [m] */,
+             double *out_eig /* [m] */, double *out_loadings /* [n_comp][m] */,
+             double *out_scores /* [n_comp][n] */, double *out_cov /* [m][m], may be NULL */,
+             int32_t *out_sweeps);
+/* The eigenpairs of the symmetric matrix a [m][m] (checked on the device: every value finite and
+ * a[i][j] == a[j][i]; MGP_E_INVALID otherwise) by cyclic two-sided Jacobi in the round-robin
+ * (tournament) order, a fixed schedule: given a, the result is the same bytes on every call.
+ * m' = m rounded up to even; a sweep is m' - 1 steps; step r pairs m' - 1 with r and every other i
+ * with (2 r - i) mod (m' - 1) (a pair with the padding index is skipped); the m' / 2 disjoint
+ * rotations of a step are computed from one snapshot: tau = (a_qq - a_pp) / (2 a_pq),
+ * t = sign(tau) / (|tau| + sqrt(1 + tau^2)), c = 1 / sqrt(1 + t^2), s = t c (p < q; the element-wise
+ * expressions of A' = J^T A J, which keep A exactly symmetric, are in csrc/mgp_pca.h). A pair
+ * rotates only if |a_pq| > 2^-53 sqrt(|a_pp|) sqrt(|a_qq|) and |a_pq| > 2^-63 max|a_ij| of the input.
+ * The iteration ends after the first sweep in which no pair rotated; *out_sweeps is the number of
+ * sweeps in which one did (0 for a diagonal matrix and for m <= 1). 60 sweeps that all rotated are
+ * MGP_E_HIP with a message of their own, never a partial result.
+ * out_eig [m] descends, ties broken by the lower index of their diagonal place; out_vec [m][m], row
+ * c the unit eigenvector of out_eig[c], flipped so that its entry of largest magnitude (the lowest
+ * index among equals) is positive.
+ * Bounds (MGP_E_INVALID before any allocation or device call): no null pointer, 0 <= m <= 2048.
+ * m == 0: nothing is launched. Device memory: 48 m^2 + 12 m bytes. */
+int  mgp_sym_eig(int device, const double *a /* [m][m] */, int64_t m, double *out_eig /* [m] */,
+                 double *out_vec /* [m][m], row c = eigenvector c */, int32_t *out_sweeps);
 /* Louvain communities of an integer-weighted graph on the device (added under ABI 7): the second
  * half of Signac's FindClonotypes, FindClusters on the SNN graph, which gives each cell its
  * clonotype. The CPU tools visit the vertices one by one in a random order; here a pass is

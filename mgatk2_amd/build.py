@@ -26,7 +26,7 @@ ORACLE_SO = ORACLE_DIR / "_build" / "liboracle.so"
 
 HIP_SOURCES = ["mgp_engine.hip", "mgp_jobs.hip", "mgp_synth.hip", "mgp_txtgz.hip", "mgp_variants.hip", "mgp_qc.hip",
                "mgp_cluster.hip", "mgp_graph.hip", "mgp_louvain.hip", "mgp_inflate.hip", "mgp_table.hip", "mgp_groups.hip",
-               "mgp_rank.hip"]
+               "mgp_rank.hip", "mgp_pca.hip"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 
 

@@ -13,7 +13,8 @@ the device, the trees and heatmap orders in variants/), and ``--neighbors K`` / 
 clonotype, in variants/), and ``--groups FILE`` / ``--group-min-cells N`` / ``--group-min-af F`` (the
 pseudobulk counts and marker variants of every cell group of FILE from the device's rows, groups/), and
 ``--group-test`` / ``--group-test-max-p P`` (the rank-sum test of each variant, every group against the rest
-of the cells, ranked on the device: groups/group_tests.tsv).
+of the cells, ranked on the device: groups/group_tests.tsv), and ``--pca N`` / ``--pca-scale`` (the first N
+principal components of the heteroplasmy matrix on the device, in variants/).
 Not carried over: ``hardmask-fasta`` (FASTA masking utility, outside the hot path).
 """
 
@@ -109,16 +110,27 @@ def _group_option_list() -> list:
     ]
 
 
+def _pca_option_list() -> list:
+    """--pca and --pca-scale, on `run`, `tenx`, `call` and `analyze`: declared beside the group options."""
+    return [
+        click.option("--pca", "pca", default=None, type=click.IntRange(min=1, max=50), metavar="N",
+                     help="The first N principal components of the heteroplasmy matrix on the device, as R's "
+                          "prcomp (variants/cell_pca.tsv, variant_loadings.tsv, pca_variance.tsv); needs --variants"),
+        click.option("--pca-scale", "pca_scale", is_flag=True,
+                     help="Scale each variant to unit variance before the components (prcomp's scale.); needs --pca"),
+    ]
+
+
 def _analysis_options(f):
-    """The group options and the analysis options alone (`analyze`: there is no BAM)."""
-    for o in reversed(_group_option_list() + _analysis_option_list()):
+    """The group and PCA options and the analysis options alone (`analyze`: there is no BAM)."""
+    for o in reversed(_group_option_list() + _pca_option_list() + _analysis_option_list()):
         f = o(f)
     return f
 
 
 def _variant_options(f):
     """The group options, the analysis options (after every reference option) and --device-inflate."""
-    opts = _group_option_list() + _analysis_option_list() + [
+    opts = _group_option_list() + _pca_option_list() + _analysis_option_list() + [
         click.option("--device-inflate", "device_inflate", is_flag=True,
                      help="Inflate the BAM's BGZF blocks on the device (the first of --devices); CRC32 stays on "
                           "the host. Off by default"),
@@ -132,13 +144,15 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
                   variant_low_coverage, variant_min_coverage, coverage_stats=False, cell_min_mean_coverage=0.0,
                   cell_min_coverage_breadth=0.0, recompute_reference=False, cluster=False, clones=None, neighbors=None,
                   snn_prune=None, clonotypes=False, clonotype_resolution=None, device_inflate=False, groups=None,
-                  group_min_cells=None, group_min_af=None, group_test=False, group_test_max_p=None) -> dict:
+                  group_min_cells=None, group_min_af=None, group_test=False, group_test_max_p=None, pca=None,
+                  pca_scale=False) -> dict:
     """The options run_pipeline gets beyond the reference's, each only when asked for: the variant
     options with --variants; the four coverage options with --coverage-stats, otherwise the filter
     thresholds and --recompute-reference that were given; the analysis options that were given (one
     that lacks what it needs, options.REQUIRES, or is out of range: a usage error); --device-inflate; --groups
     and the thresholds given with it (one given without --groups: a usage error); --group-test (without --groups:
-    a usage error) and --group-test-max-p when given (without --group-test: a usage error)."""
+    a usage error) and --group-test-max-p when given (without --group-test: a usage error); --pca (without
+    --variants: a usage error) and --pca-scale (without --pca: a usage error)."""
     from .options import AnalysisOptions
 
     opts = AnalysisOptions(call_variants, cluster, clones, neighbors, snn_prune, clonotypes, clonotype_resolution)
@@ -180,6 +194,14 @@ def _variant_args(call_variants, variant_min_cells, variant_min_strand_cor, vari
         out.update(groups=str(groups))
         out.update({k: v for k, v in (("group_min_cells", group_min_cells), ("group_min_af", group_min_af))
                     if v is not None})
+    if pca is not None and not call_variants:
+        raise click.UsageError("--pca requires --variants")
+    if pca_scale and pca is None:
+        raise click.UsageError("--pca-scale requires --pca")
+    if pca is not None:
+        out.update(pca=int(pca))
+        if pca_scale:
+            out.update(pca_scale=True)
     return out
 
 
@@ -401,6 +423,9 @@ def run_pipeline_command(bam_path, output_dir, barcode_file, barcode_tag, min_ba
                         variant_args.get("group_min_cells", 2), variant_args.get("group_min_af", 0.01))
         if variant_args and variant_args.get("group_test"):
             logger.info("  Group rank-sum tests:   max p %s", variant_args.get("group_test_max_p", 0.01))
+        if variant_args and variant_args.get("pca") is not None:
+            logger.info("  Principal components:   %s, scaled %s", variant_args["pca"],
+                        variant_args.get("pca_scale", False))
         if variant_args and variant_args.get("device_inflate"):
             logger.info("  BGZF inflate:           on the device")
         if dry_run:

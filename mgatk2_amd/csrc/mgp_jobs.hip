@@ -7,10 +7,12 @@
 // *_rows form on u32 rows of the caller's (on_rows). The clustering of the heteroplasmy
 // matrix (mgp_cluster.hip) reads no rows and needs no context: mgp_pair_dist / mgp_hclust*;
 // nor do the cells' neighbour graphs (mgp_graph.hip): mgp_knn / mgp_snn; nor the communities of
-// such a graph (mgp_louvain.hip): mgp_louvain.
+// such a graph (mgp_louvain.hip): mgp_louvain; nor the matrix's principal components
+// (mgp_pca.hip): mgp_pca / mgp_sym_eig.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -23,6 +25,7 @@
 #include "mgp_host.h"
 #include "mgp_jobs.h"
 #include "mgp_louvain.h"
+#include "mgp_pca.h"
 #include "mgp_qc.h"
 #include "mgp_rank.h"
 #include "mgp_txtgz.h"
@@ -78,6 +81,12 @@ struct GraphState {
 // mgp_rank_sums: the rank sums' buffers (mgp_rank.hip), a call's own
 struct RankState {
     DevBuf x, group, keys, pay, r2, pos, ties, bad;
+};
+
+// mgp_pca / mgp_sym_eig: the principal components' buffers (mgp_pca.hip), a call's own
+struct PcaState {
+    DevBuf x, z, part, mean, var, sd, covp, cov, scores, bad;  // mgp_pca
+    DevBuf a[2], v[2], vec, perm, maxabs, flag;                // the eigensolver: A and V ping-ponged
 };
 
 // mgp_louvain: the community detection's buffers (mgp_louvain.hip), a call's own
@@ -1372,6 +1381,181 @@ int mgp_rank_sums(int device, const double* x, int64_t n_items, int64_t n_feat, 
         if (std::getenv("MGP_VAR_PROF"))
             std::fprintf(stderr, "[%s] %lld x %lld items x features, %d groups, tile %d, batch %lld: kernels %.3f ms\n", who,
                          (long long)n_items, (long long)n_feat, (int)n_groups, tile, (long long)batch, kernel_ms);
+        return (int)MGP_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// mgp_sym_eig / mgp_pca: the eigenpairs of a symmetric matrix by the fixed-order Jacobi iteration of
+// mgp_pca.h, and the principal components of the heteroplasmy matrix's columns with it (R's
+// prcomp(t(af)), the vignette's "dimensionality reduction"). No engine context, as the graphs: a
+// call has its own stream and buffers, all freed when it returns. Per sweep only the "rotated" word
+// comes back; the eigenvalues are put in order here (a stable sort of m numbers), everything else
+// runs on the device.
+// ---------------------------------------------------------------------------
+// the eigenpairs of st.a[0] [m][m] (overwritten): out_eig [m] descending (ties: the lower diagonal
+// place first), st.vec [k][m] the first k vectors with the sign rule applied, *out_sweeps
+static int pca_eig(PcaState& st, hipStream_t s, const char* who, int m, int k, double* out_eig, int32_t* out_sweeps) {
+    const size_t mm = (size_t)m * (size_t)m;
+    MGP_TRY(st.a[1].ensure(mm * 8));
+    MGP_TRY(st.v[0].ensure(mm * 8));
+    MGP_TRY(st.v[1].ensure(mm * 8));
+    MGP_TRY(st.vec.ensure((size_t)k * (size_t)m * 8));
+    MGP_TRY(st.perm.ensure((size_t)m * 4));
+    MGP_TRY(st.bad.ensure(4));
+    MGP_TRY(st.maxabs.ensure(8));
+    MGP_TRY(st.flag.ensure(4));
+    HIP_TRY(hipMemsetAsync(st.bad.p, 0, 4, s));
+    HIP_TRY(hipMemsetAsync(st.maxabs.p, 0, 8, s));
+    if (pca::sym_check(st.a[0].as<double>(), m, st.bad.as<uint32_t>(), st.maxabs.as<unsigned long long>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": check kernel launch failed");
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bad & pca::BAD_VALUE) return set_err(MGP_E_INVALID, std::string(who) + ": a value of the matrix is not finite");
+    if (bad) return set_err(MGP_E_INVALID, std::string(who) + ": the matrix is not symmetric");
+    if (pca::identity(st.v[0].as<double>(), m, s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    int cur = 0, sweeps = 0;
+    const int steps = m < 2 ? 0 : ((m + 1) & ~1) - 1;
+    bool done = steps == 0;
+    for (int sweep = 0; sweep < pca::kMaxSweeps && !done; ++sweep) {
+        HIP_TRY(hipMemsetAsync(st.flag.p, 0, 4, s));
+        for (int step = 0; step < steps; ++step, cur ^= 1)
+            if (pca::jacobi_step(st.a[cur].as<double>(), st.v[cur].as<double>(), st.a[cur ^ 1].as<double>(),
+                                 st.v[cur ^ 1].as<double>(), m, step, st.maxabs.as<unsigned long long>(),
+                                 st.flag.as<uint32_t>(), s) != 0)
+                return set_err(MGP_E_HIP, std::string(who) + ": Jacobi kernel launch failed");
+        uint32_t rotated = 0;
+        HIP_TRY(hipMemcpyAsync(&rotated, st.flag.p, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (rotated)
+            ++sweeps;
+        else
+            done = true;
+    }
+    if (!done)
+        return set_err(MGP_E_HIP, std::string(who) + ": the Jacobi iteration still rotated in sweep " +
+                                      std::to_string(pca::kMaxSweeps) + " (no result is returned)");
+    std::vector<double> diag((size_t)m);
+    HIP_TRY(hipMemcpy2DAsync(diag.data(), 8, st.a[cur].p, ((size_t)m + 1) * 8, 8, (size_t)m, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<int32_t> perm((size_t)m);
+    for (int i = 0; i < m; ++i) {
+        perm[(size_t)i] = i;
+        if (!(std::abs(diag[(size_t)i]) <= 1.7976931348623157e308))
+            return set_err(MGP_E_INVALID, std::string(who) + ": the iteration overflowed (entries too large)");
+    }
+    std::stable_sort(perm.begin(), perm.end(),
+                     [&](int32_t x, int32_t y) { return diag[(size_t)x] > diag[(size_t)y]; });
+    for (int c = 0; c < m; ++c) out_eig[c] = diag[(size_t)perm[(size_t)c]];
+    HIP_TRY(hipMemcpyAsync(st.perm.p, perm.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // (perm is this frame's)
+    if (pca::order_vectors(st.v[cur].as<double>(), st.perm.as<int32_t>(), m, k, st.vec.as<double>(), s) != 0)
+        return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+    *out_sweeps = sweeps;
+    return MGP_OK;
+}
+
+int mgp_sym_eig(int device, const double* a, int64_t m, double* out_eig, double* out_vec, int32_t* out_sweeps) {
+    const char* who = "mgp_sym_eig";
+    if (m < 0) return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    if (m > pca::kMaxFeat) return set_err(MGP_E_INVALID, std::string(who) + ": more than 2048 features in one call");
+    if (!out_sweeps || (m > 0 && (!a || !out_eig || !out_vec)))
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    *out_sweeps = 0;
+    if (m == 0) return MGP_OK;
+    return cl_call<PcaState>(device, [&](PcaState& st, hipStream_t s) {
+        const size_t mm = (size_t)m * (size_t)m;
+        MGP_TRY(st.a[0].ensure(mm * 8));
+        HIP_TRY(hipMemcpyAsync(st.a[0].p, a, mm * 8, hipMemcpyHostToDevice, s));
+        VarProf prof(s);
+        MGP_TRY(pca_eig(st, s, who, (int)m, (int)m, out_eig, out_sweeps));
+        prof.stop();
+        HIP_TRY(hipMemcpyAsync(out_vec, st.vec.p, mm * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        prof.report(who, (std::string("rows x sweeps, Jacobi")).c_str(), m, *out_sweeps);
+        return (int)MGP_OK;
+    });
+}
+
+int mgp_pca(int device, const double* x, int64_t n_items, int64_t n_feat, int32_t scale, int32_t n_comp,
+            double* out_mean, double* out_sd, double* out_eig, double* out_loadings, double* out_scores,
+            double* out_cov, int32_t* out_sweeps) {
+    const char* who = "mgp_pca";
+    if (n_items < 0 || n_feat < 0) return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    if (n_items > pca::kMaxItems) return set_err(MGP_E_INVALID, std::string(who) + ": more than 2^20 items in one call");
+    if (n_feat > pca::kMaxFeat) return set_err(MGP_E_INVALID, std::string(who) + ": more than 2048 features in one call");
+    if (n_items < 2) return set_err(MGP_E_INVALID, std::string(who) + ": at least 2 items are needed");
+    if (n_comp < 1) return set_err(MGP_E_INVALID, std::string(who) + ": n_comp must be at least 1");
+    if (n_comp > std::min(n_feat, n_items - 1))
+        return set_err(MGP_E_INVALID, std::string(who) + ": n_comp must be at most min(n_feat, n_items - 1)");
+    if (!x || !out_mean || (scale && !out_sd) || !out_eig || !out_loadings || !out_scores || !out_sweeps)
+        return set_err(MGP_E_INVALID, std::string(who) + ": bad arguments");
+    *out_sweeps = 0;
+    const int tile = pca::cov_tile((int)n_feat, lv_env("MGP_PCA_TILE", 16, 64, 0));  // (changes no result)
+    return cl_call<PcaState>(device, [&](PcaState& st, hipStream_t s) {
+        const int n = (int)n_items, m = (int)n_feat, k = n_comp, S = pca::slabs(n_items);
+        const size_t un = (size_t)n, um = (size_t)m, mm = um * um;
+        MGP_TRY(st.x.ensure(un * um * 8));
+        MGP_TRY(st.z.ensure(un * um * 8));
+        MGP_TRY(st.part.ensure((size_t)S * um * 8));
+        MGP_TRY(st.mean.ensure(um * 8));
+        MGP_TRY(st.var.ensure(um * 8));
+        MGP_TRY(st.sd.ensure(um * 8));
+        MGP_TRY(st.covp.ensure((size_t)S * mm * 8));
+        MGP_TRY(st.cov.ensure(mm * 8));
+        MGP_TRY(st.a[0].ensure(mm * 8));
+        MGP_TRY(st.scores.ensure((size_t)k * un * 8));
+        MGP_TRY(st.bad.ensure(4));
+        HIP_TRY(hipMemcpyAsync(st.x.p, x, un * um * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(st.bad.p, 0, 4, s));
+        const double *dx = st.x.as<double>(), *mean = st.mean.as<double>();
+        const double* sd = scale ? st.sd.as<double>() : nullptr;
+        VarProf p_mean(s);
+        if (pca::slab_sums(dx, nullptr, n, m, st.part.as<double>(), st.bad.as<uint32_t>(), s) != 0 ||
+            pca::slab_reduce(st.part.as<double>(), m, S, (double)n, st.mean.as<double>(), nullptr, s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+        uint32_t bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, st.bad.p, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (bad) return set_err(MGP_E_INVALID, std::string(who) + ": a value of x is not finite");
+        if (scale && (pca::slab_sums(dx, mean, n, m, st.part.as<double>(), st.bad.as<uint32_t>(), s) != 0 ||
+                      pca::slab_reduce(st.part.as<double>(), m, S, (double)(n - 1), st.var.as<double>(),
+                                       st.sd.as<double>(), s) != 0))
+            return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+        if (pca::standardize(dx, mean, sd, n, m, st.z.as<double>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": kernel launch failed");
+        p_mean.stop();
+        VarProf p_cov(s);
+        if (pca::covariance(st.z.as<double>(), n, m, tile, st.covp.as<double>(), st.cov.as<double>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": covariance kernel launch failed");
+        p_cov.stop();
+        HIP_TRY(hipMemcpyAsync(st.a[0].p, st.cov.p, mm * 8, hipMemcpyDeviceToDevice, s));
+        VarProf p_eig(s);
+        MGP_TRY(pca_eig(st, s, who, m, k, out_eig, out_sweeps));
+        p_eig.stop();
+        VarProf p_sc(s);
+        if (pca::scores(st.z.as<double>(), st.vec.as<double>(), n, m, k, st.scores.as<double>(), s) != 0)
+            return set_err(MGP_E_HIP, std::string(who) + ": scores kernel launch failed");
+        p_sc.stop();
+        HIP_TRY(hipMemcpyAsync(out_mean, st.mean.p, um * 8, hipMemcpyDeviceToHost, s));
+        if (scale) {
+            HIP_TRY(hipMemcpyAsync(out_sd, st.sd.p, um * 8, hipMemcpyDeviceToHost, s));
+        } else if (out_sd) {  // the covariance's diagonal, its square root taken below
+            HIP_TRY(hipMemcpy2DAsync(out_sd, 8, st.cov.p, (um + 1) * 8, 8, um, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipMemcpyAsync(out_loadings, st.vec.p, (size_t)k * um * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_scores, st.scores.p, (size_t)k * un * 8, hipMemcpyDeviceToHost, s));
+        if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, st.cov.p, mm * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (!scale && out_sd)
+            for (size_t f = 0; f < um; ++f) out_sd[f] = std::sqrt(out_sd[f]);
+        p_mean.report(who, "items x features, means and scaling", n_items, n_feat);
+        p_cov.report(who, (std::string("items x features, covariance, tile ") + std::to_string(tile)).c_str(), n_items,
+                     n_feat);
+        p_eig.report(who, "features x sweeps, Jacobi", n_feat, *out_sweeps);
+        p_sc.report(who, "items x components, scores", n_items, n_comp);
         return (int)MGP_OK;
     });
 }

@@ -48,7 +48,7 @@ ABI_SYMBOLS = (
     "mgp_knn", "mgp_snn", "mgp_louvain", "mgp_bgzf_inflate", "mgp_inflater_create", "mgp_inflater_destroy",
     "mgp_inflater_run", "mgp_inflater_host_alloc", "mgp_inflater_host_release", "mgp_inflater_times",
     "mgp_zlib_inflate", "mgp_open_table", "mgp_table_load", "mgp_table_load_planes", "mgp_table_check",
-    "mgp_table_ready", "mgp_group_moments_run", "mgp_rows_group_moments", "mgp_rank_sums",
+    "mgp_table_ready", "mgp_group_moments_run", "mgp_rows_group_moments", "mgp_rank_sums", "mgp_pca", "mgp_sym_eig",
 )
 ABI_VERSION = 7
 CFG_KEEP_TN5 = 0x1
@@ -359,6 +359,8 @@ def load_library(path: Path | None = None) -> C.CDLL:
         "mgp_knn": ([C.c_int, vp, i64, i64, i32, vp, vp], C.c_int),
         "mgp_rank_sums": ([C.c_int, vp, i64, i64, vp, i32, vp, vp, vp], C.c_int),
         "mgp_snn": ([C.c_int, vp, i64, i32, i32, i64, C.POINTER(i64), vp, vp, vp], C.c_int),
+        "mgp_pca": ([C.c_int, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i32)], C.c_int),
+        "mgp_sym_eig": ([C.c_int, vp, i64, vp, vp, C.POINTER(i32)], C.c_int),
         "mgp_louvain": (
             [C.c_int, i64, i64, vp, vp, vp, C.c_double, i32, i32, vp, C.POINTER(i64), C.POINTER(C.c_double), vp,
              C.POINTER(i32), vp], C.c_int
@@ -467,6 +469,7 @@ class EngineResult:
     neighbors: object | None = None  # neighbor_result: the NeighborGraph
     clonotypes: object | None = None  # clonotype_result: the Clonotypes
     groups: object | None = None  # enable_groups: the GroupResult (analysis/groups.py)
+    pca: object | None = None  # enable_pca: the PcaResult (analysis/pca.py)
 
     @staticmethod
     def alloc(n_cells: int, L: int, dense: bool = True) -> EngineResult:
@@ -996,6 +999,49 @@ def rank_sums(x, group, n_groups: int, device: int = 0) -> dict:
     _ck(load_library().mgp_rank_sums(int(device), _ptr(x), n, nf, _ptr(group), n_groups, _ptr(out["r2"]),
                                      _ptr(out["pos"]), _ptr(out["ties"])), "mgp_rank_sums")
     return out
+
+
+PCA_MAX_ITEMS = 1 << 20  # items of one mgp_pca call
+PCA_MAX_FEAT = 2048      # features of one mgp_pca call, rows of one mgp_sym_eig call
+PCA_SLAB = 1024          # items of a slab of the sums (part of the definition, pca::kSlab)
+
+
+def pca(x, n_comp: int, scale: bool = False, device: int = 0, want_cov: bool = False) -> dict:
+    """mgp_pca: the principal components of the columns of x [n_feat, n_items] (fp64, every value finite), R's
+    prcomp(t(x), center = TRUE, scale. = scale), every number a fixed chain of fp64 operations (include/mgpileup.h).
+    A dict: `mean` [m], `sd` [m] (the divisor with scale, otherwise the square root of the covariance's diagonal),
+    `eigenvalues` [m] descending, `loadings` [n_comp, m], `scores` [n_comp, n], `sweeps`, and `cov` [m, m] when
+    asked for. 2 <= n_items <= PCA_MAX_ITEMS, n_feat <= PCA_MAX_FEAT, 1 <= n_comp <= min(n_feat, n_items - 1)."""
+    x = _cluster_x(x)
+    m, n = x.shape
+    k = int(n_comp)
+    ok = 2 <= n <= PCA_MAX_ITEMS and m <= PCA_MAX_FEAT and 1 <= k <= min(m, n - 1)  # (otherwise refused before any use)
+    out = {"mean": np.zeros(m if ok else 0), "sd": np.zeros(m if ok else 0), "eigenvalues": np.zeros(m if ok else 0),
+           "loadings": np.zeros((k, m) if ok else (0, 0)), "scores": np.zeros((k, n) if ok else (0, 0))}
+    cov = np.zeros((m, m)) if ok and want_cov else None
+    sweeps = C.c_int32(0)
+    _ck(load_library().mgp_pca(int(device), _ptr(x), n, m, int(bool(scale)), k, _ptr(out["mean"]), _ptr(out["sd"]),
+                               _ptr(out["eigenvalues"]), _ptr(out["loadings"]), _ptr(out["scores"]), _ptr(cov),
+                               C.byref(sweeps)), "mgp_pca")
+    out["sweeps"] = int(sweeps.value)
+    if want_cov:
+        out["cov"] = cov
+    return out
+
+
+def sym_eig(a, device: int = 0):
+    """mgp_sym_eig: (eigenvalues [m] descending, vectors [m, m] with row c the eigenvector c, sweeps) of the
+    symmetric finite matrix a [m, m] by the fixed-order Jacobi iteration on the device (include/mgpileup.h); the
+    same bytes on every call. m <= PCA_MAX_FEAT."""
+    a = np.ascontiguousarray(a, np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise InvalidInputError("a is [m, m]")
+    m = a.shape[0]
+    ok = m <= PCA_MAX_FEAT  # (otherwise refused before any use)
+    eig, vec = np.zeros(m if ok else 0), np.zeros((m, m) if ok else (0, 0))
+    sweeps = C.c_int32(0)
+    _ck(load_library().mgp_sym_eig(int(device), _ptr(a), m, _ptr(eig), _ptr(vec), C.byref(sweeps)), "mgp_sym_eig")
+    return eig, vec, int(sweeps.value)
 
 
 LOUVAIN_MAX_VERTICES = 1 << 20  # vertices of one mgp_louvain call

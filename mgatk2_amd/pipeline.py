@@ -129,6 +129,22 @@ def analysis_settings(call_variants=False, variant_min_cells=5, variant_min_stra
     return s
 
 
+def pca_settings(call_variants=False, pca=None, pca_scale=False) -> dict:
+    """The PCA keywords of run_pipeline / analyze_outputs checked (InvalidInputError), beside analysis_settings
+    (whose own keywords end with the groups'): the principal components of the heteroplasmy matrix, off unless
+    asked for; variants/cell_pca.tsv, variant_loadings.tsv and pca_variance.tsv in the output."""
+    s: dict[str, Any] = {"pca": None, "pca_scale": bool(pca_scale)}
+    if pca is not None:
+        from .analysis.pca import check_pca
+
+        if not call_variants:
+            raise InvalidInputError("pca requires call_variants")
+        s["pca"] = check_pca(pca)
+    elif s["pca_scale"]:
+        raise InvalidInputError("pca_scale requires pca")
+    return s
+
+
 def enable_analyses(processor, s, names=None) -> None:
     """Turn on, on a CellProcessor, the analyses that `s` (an object with analysis_settings' names) asks for.
     names: the barcode of each cell of the run (of each column of a loaded table), for the groups."""
@@ -147,6 +163,8 @@ def enable_analyses(processor, s, names=None) -> None:
 
         processor.enable_groups(*resolve_groups(s.groups, list(names or [])), s.group_min_cells, s.group_min_af,
                                 getattr(s, "group_test", False), getattr(s, "group_test_max_p", 0.01))
+    if getattr(s, "pca", None) is not None:
+        processor.enable_pca(s.pca, getattr(s, "pca_scale", False))
 
 
 def write_table_outputs(processor, res, names: list[str], output_dir, output_format: str, coverage_on: bool,
@@ -198,6 +216,20 @@ def write_stage_outputs(processor, res, af_names: list[str], output_dir) -> None
                 logger.info(*line)
 
 
+def write_pca_outputs(processor, res, af_names: list[str], output_dir) -> None:
+    """The principal components of the heteroplasmy matrix, when on (analysis/pca.py): made on the first
+    device and written to variants/."""
+    if processor.pca_opt is None or res.variants is None:
+        return
+    from .analysis.pca import write_pca_outputs as write_files
+
+    result = processor.pca_result(res)
+    write_files(result, af_names, res.variants, output_dir)
+    if result.scores is not None:
+        logger.info("PCA: %d cells x %d variants, %d components, %d Jacobi sweeps", result.n,
+                    result.loadings.shape[1], result.n_comp, result.sweeps)
+
+
 class MtDNAPipeline:
     """Single-pass mtDNA genotyping pipeline (pipeline.py:23-74)."""
 
@@ -238,6 +270,8 @@ class MtDNAPipeline:
         group_min_af: float = 0.01,
         group_test: bool = False,
         group_test_max_p: float = 0.01,
+        pca: int | None = None,
+        pca_scale: bool = False,
     ):
         self.bam_path = Path(bam_path)
         # streamed ingest (default; MGP_STREAM=0 decodes the whole chrM set first)
@@ -259,6 +293,7 @@ class MtDNAPipeline:
             variant_low_coverage, variant_min_coverage, coverage_stats, cell_min_mean_coverage,
             cell_min_coverage_breadth, recompute_reference, cluster, clones, neighbors, snn_prune, clonotypes,
             clonotype_resolution, group_test, group_test_max_p, groups, group_min_cells, group_min_af))
+        vars(self).update(pca_settings(call_variants, pca, pca_scale))
         self.timings: dict[str, float] = {}
         self.engine_result = None
         self.read_stats: dict = {}
@@ -383,6 +418,7 @@ class MtDNAPipeline:
         # last, so that a population above an analysis's bound raises with every other output
         # written; the run's engine contexts closed long ago
         write_stage_outputs(processor, res, af_names, self.output_dir)
+        write_pca_outputs(processor, res, af_names, self.output_dir)
         t5 = time.time()
         # streamed: bam_ingest ends with the last decoded batch and `engine` is only what the
         # device still did after it (the rest ran under the decode)
@@ -450,6 +486,8 @@ def run_pipeline(
     group_min_af: float = 0.01,
     group_test: bool = False,
     group_test_max_p: float = 0.01,
+    pca: int | None = None,
+    pca_scale: bool = False,
 ) -> dict[str, Any]:
     """pipeline.py:183-269. ``min_distance_from_end`` is accepted and, as in the
     reference, not passed on (the engine uses 5). ``call_variants``
@@ -475,7 +513,10 @@ def run_pipeline(
     exceeds the rest of the population's (this project's thresholds; mgatk defines none). ``group_test`` (needs
     ``groups``) adds groups/group_tests.tsv: the Wilcoxon rank-sum test of each marker or called variant's
     heteroplasmy over the cells, every group against the rest (Seurat's FindAllMarkers; the ranks on the device),
-    the pairs higher in the group with a p-value up to ``group_test_max_p``."""
+    the pairs higher in the group with a p-value up to ``group_test_max_p``. ``pca`` = N (needs ``call_variants``;
+    1..50, clipped to what the matrix has) writes the first N principal components of the heteroplasmy matrix,
+    R's prcomp(t(af)) on the device with a fixed operation order: variants/cell_pca.tsv, variant_loadings.tsv and
+    pca_variance.tsv; ``pca_scale`` (needs ``pca``) scales each variant to unit variance first."""
     barcode_metadata = None
     if barcode_file is None:
         from .file_io.barcode_extraction import extract_barcodes_from_bam
@@ -519,7 +560,7 @@ def run_pipeline(
         recompute_reference=recompute_reference, cluster=cluster, clones=clones,
         neighbors=neighbors, snn_prune=snn_prune, clonotypes=clonotypes, clonotype_resolution=clonotype_resolution,
         groups=groups, group_min_cells=group_min_cells, group_min_af=group_min_af, group_test=group_test,
-        group_test_max_p=group_test_max_p,
+        group_test_max_p=group_test_max_p, pca=pca, pca_scale=pca_scale,
     )
     return pipeline.run()
 
@@ -544,7 +585,7 @@ def _subset_columns(file_barcodes: list[str], barcodes) -> tuple[Any, list[str]]
 
 
 def analyze_outputs(input_dir, output_dir=None, barcodes=None, device: int = 0, host_inflate: bool = False,
-                    **analysis) -> dict[str, Any]:
+                    pca=None, pca_scale=False, **analysis) -> dict[str, Any]:
     """The analyses of a run (``analysis``: run_pipeline's keywords from call_variants to
     clonotype_resolution, with its defaults and rules) from the count files a run left in
     ``input_dir`` (output/counts.h5 and output/metadata.h5, ours or the reference tool's): the
@@ -553,13 +594,15 @@ def analyze_outputs(input_dir, output_dir=None, barcodes=None, device: int = 0, 
     column of the files is a cell, the reference alleles are the files', and the values are
     the stored min(count, 65535): the results equal R's on the files exactly, and a run's own
     wherever no count saturates. ``groups`` (with ``group_min_cells``, ``group_min_af``, ``group_test``,
-    ``group_test_max_p``) labels the files' columns. Writes coverage/, variants/ and groups/ into ``output_dir`` (default:
+    ``group_test_max_p``) labels the files' columns; ``pca`` / ``pca_scale`` as run_pipeline's.
+    Writes coverage/, variants/ and groups/ into ``output_dir`` (default:
     ``input_dir``); the count files are never rewritten. ``host_inflate``: libhdf5 inflates
     the chunks instead of the device (the same results)."""
     from .engine import EngineResult
     from .table import load_counts
 
-    s = SimpleNamespace(**analysis_settings(**analysis))
+    s = SimpleNamespace(**analysis_settings(**analysis),
+                        **pca_settings(analysis.get("call_variants", False), pca, pca_scale))
     t0 = time.time()
     out_dir = Path(output_dir) if output_dir else Path(input_dir)
     with load_counts(input_dir, device=device, host_inflate=host_inflate) as loaded:
@@ -581,6 +624,7 @@ def analyze_outputs(input_dir, output_dir=None, barcodes=None, device: int = 0, 
                                    s.call_variants)
     write_group_outputs(res, out_dir)
     write_stage_outputs(processor, res, af_names, out_dir)
+    write_pca_outputs(processor, res, af_names, out_dir)
     t3 = time.time()
     timings = {"load": t1 - t0, **{"load_" + k: v for k, v in loaded.seconds.items()}, "analyses": t2 - t1,
                "write": t3 - t2, "total": t3 - t0, **tail, **processor.last_timing}

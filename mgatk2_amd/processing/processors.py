@@ -159,6 +159,7 @@ class CellProcessor:
         self.variants_opt: dict | None = None
         self.coverage_opt: dict | None = None
         self.groups_opt: dict | None = None
+        self.pca_opt: dict | None = None
         self.stage_opt: dict[str, dict] = {}  # the analyses turned on (enable), by stage key
         # what a loaded table sets (analyze_outputs): the file's reference alleles in place of the
         # tally's, and the population in place of every cell (a subset of the file's columns)
@@ -244,6 +245,31 @@ class CellProcessor:
 
     def enable_clonotypes(self, resolution: float = 1.0):
         self.enable("clonotypes", resolution=resolution)
+
+    def enable_pca(self, n_comp: int, scale: bool = False):
+        """The principal components of the run's heteroplasmy matrix (mgp_pca; analysis/pca.py), made by
+        pca_result: the first n_comp (1..50, clipped to what the matrix has), the variants scaled to unit
+        variance with `scale`. Needs enable_variants (InvalidInputError otherwise)."""
+        from ..analysis.pca import check_pca
+
+        if self.variants_opt is None:
+            raise InvalidInputError("pca requires call_variants")
+        self.pca_opt = dict(n_comp=check_pca(n_comp), scale=bool(scale))
+
+    def pca_result(self, res: EngineResult):
+        """The principal components of a finished run's matrix (res.allele_freq with res.variants' names), on
+        the first device, after the run's engine contexts have closed, as stage_result. Sets res.pca and
+        last_timing["pca"]; returns the PcaResult (None when not enabled)."""
+        if self.pca_opt is None:
+            return None
+        from ..analysis.pca import principal_components
+
+        t0 = time.perf_counter()
+        try:
+            res.pca = principal_components(res.allele_freq, table=res.variants, device=self.devices[0], **self.pca_opt)
+        finally:
+            self.last_timing["pca"] = time.perf_counter() - t0
+        return res.pca
 
     cluster_result = partialmethod(stage_result, "cluster")
     neighbor_result = partialmethod(stage_result, "neighbors")
